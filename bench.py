@@ -1,9 +1,14 @@
 #!/usr/bin/env python
 """bench.py — particle-samples/s of one MENT-Flow training step on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong]
+    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline figure needs and nothing else: set up, W warm-up steps, ONE timed region of K steps,
+the outputs of the last timed step under DIR if ``--dump-outputs`` is given, the JSON line.  ``--full`` adds everything
+else the benchmark measures or checks: the parity gate against the fp64 oracle, per-kernel HIP-event timing and the
+rooflines, the `strong_n1` object, the CPU baseline, and 5 timed regions instead of 1 (the median is reported).
 
 With ``--gpus N > 1`` and no WORLD_SIZE in the environment the script starts its N ranks itself: the parent is a pure
 launcher (no torch import, no HIP call) that spawns N fresh children with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set,
@@ -16,9 +21,9 @@ loss.backward(); AdamW.step() — on synthetic data of BASELINE.json's headline 
 penalty 500).  ``--scaling weak`` (default): 2 097 152 particles per GPU (C4's 16 M-particle batch over 8 GPUs);
 ``--scaling strong``: C4's global 16 777 216-particle batch divided over the N ranks (N = 1: all of it on one GPU).
 The timed region (K steps between barrier + synchronize) is repeated ``--repeats`` times; the JSON line reports the
-MEDIAN region (max over ranks of each region first) and the spread.  Rank 0 prints ONE JSON line with the throughput, the
-roofline of the dominant kernel (HIP-event timed inside the timed regions) and — at N = 1 — the CPU baseline (the oracle
-restatement of the reference timed on this host's cores).
+MEDIAN region (max over ranks of each region first) and the spread.  Rank 0 prints ONE JSON line with the throughput and,
+with ``--full``, the roofline of the dominant kernel (HIP-event timed inside the timed regions) and — at N = 1 — the CPU
+baseline (the oracle restatement of the reference timed on this host's cores).
 """
 from __future__ import annotations
 
@@ -37,7 +42,7 @@ PEAK_HBM = 8000.0              # GB/s spec
 # 64-bit LDS atomic adds a CU sustains per clock with enough waves in flight, whatever the address pattern
 # (tools/ubench_lds_atomics2.hip on MI355X, profiles/r02_ubench_lds_atomics2.txt: 3.8-3.9 lane-ops/clk/CU): the KDE
 # forward kernels are bound by this, not by HBM
-LDS_ATOMIC_U64_PER_CLK_CU = 3.9
+LDS_U64_ATOMICS_PER_CLK_CU = 3.9
 CLOCK_GHZ = 2.4
 NUM_CU = 256
 # KDE backward kernels: bound by vector-instruction ISSUE, not by HBM (76 GB/s of row traffic).  Instruction mix of the inner
@@ -83,9 +88,16 @@ def log(msg: str) -> None:
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=40)
+    ap.add_argument("--steps", type=int, default=40, help="timed steps per timed region")
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=5, help="timed regions of --steps steps each; the median is reported")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of --steps steps each; the median is reported (default: 1, with --full 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: parity gate vs the fp64 oracle, "
+                         "per-kernel HIP-event timing and rooflines, strong_n1, CPU baseline (off by default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (loss, entropy, discrepancies, parameters after the "
+                         "optimizer step, their gradients) as DIR/<name>.npy in float32")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"])
     ap.add_argument("--workload", default="c4", choices=sorted(WORKLOADS))
     ap.add_argument("--per-gpu", type=int, default=None, help="particles per GPU (overrides the scaling mode's batch)")
@@ -105,7 +117,10 @@ def parse_args(argv=None):
     # test infrastructure only: run the ranks on the host-emulated kernel build (tests/emu) so that the launcher and the
     # multi-rank plumbing can be exercised in a GPU-less container.  The line it prints is marked as emulated.
     ap.add_argument("--test-emulator-lib", default=None, help=argparse.SUPPRESS)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    return args
 
 
 # ===================================================================================================== launcher
@@ -389,6 +404,36 @@ def pipe_util_from_profile(name: str, workload: str, per_gpu: int, act_level: in
                       "busy cycles / (GRBM_GUI_ACTIVE / 8 XCDs x 1024 SIMDs); constant of that run", **meta}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path: str, model, outs, graph: bool) -> dict:
+    """What the last timed step handed its caller, as float32 DIR/<name>.npy: MENTFlow.loss's (L, H, D) — D per measurement,
+    or its mean where the step is a graph replay (GraphedTrainStep.step) — and the parameters after the optimizer step with
+    the gradients that step applied, flattened in model.parameters() order.  The inputs are seeded: the same arguments
+    give the same inputs, so two builds can be compared output for output."""
+    import numpy as np
+    import torch
+    L, H, D = outs
+    params = list(model.parameters())
+    arrays = {"loss": L, "entropy": H}
+    if graph:
+        arrays["discrepancy_mean"] = D
+    else:
+        arrays["discrepancy"] = torch.stack([torch.as_tensor(d).detach().reshape(()) for d in D])
+    arrays["parameters"] = torch.cat([p.detach().reshape(-1) for p in params])
+    arrays["gradients"] = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1)
+                                     for p in params])
+    arrays = {k: np.asarray(torch.as_tensor(v).detach().float().cpu().numpy(), dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {k: list(a.shape) for k, a in arrays.items()}
+
+
 def run_worker(args) -> int:
     import torch
 
@@ -450,14 +495,14 @@ def run_worker(args) -> int:
         gstep = mf.graph.GraphedTrainStep(model, opt, global_batch)
 
         def step():
-            return gstep.step()[0]
+            return gstep.step()
     else:
         def step():
             opt.zero_grad()
             L, H, D = model.loss(global_batch)
             L.backward()
             opt.step()
-            return L
+            return L, H, D
 
     # evidence that the collective really spans the ranks: all-reduce of ones over the production backend
     ranks_seen = 1
@@ -470,21 +515,22 @@ def run_worker(args) -> int:
 
     # parity gate on the INITIAL parameters (before any optimizer step), fixed gates: a failure fails the run
     parity0 = None
-    if not args.no_cpu_baseline and world == 1 and not emulated and rank == 0:
+    if args.full and not args.no_cpu_baseline and world == 1 and not emulated and rank == 0:
         parity0 = parity_gate(prob, gated=True)
 
     for _ in range(args.warmup):
         step()
     region_s = []
     rank_s = []
-    _lib.prof_enable(True)
+    if args.full:
+        _lib.prof_enable(True)
     for rep in range(max(1, args.repeats)):
         sync()
         mfdist.barrier()
         sync()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            L = step()
+            outs = step()
         sync()
         mfdist.barrier()
         sync()
@@ -500,17 +546,22 @@ def run_worker(args) -> int:
             el = max(per_rank)
         region_s.append(el)
         rank_s.append(per_rank)
-    prof = _lib.prof_report()
-    _lib.prof_enable(False)
-    final_loss = float(L.detach())
+    prof = {}
+    if args.full:
+        prof = _lib.prof_report()
+        _lib.prof_enable(False)
+    final_loss = float(outs[0].detach())
     total_steps = args.steps * len(region_s)
+    if args.dump_outputs and rank == 0:
+        shapes = dump_outputs(args.dump_outputs, model, outs, bool(args.graph))       # before anything below moves the model
+        log(f"outputs of the last timed step written to {args.dump_outputs}: {shapes}")
 
     # The metric's own full-size configuration in the same record: C4's GLOBAL batch (16 777 216 particles, the N = 1 point of
     # the strong-scaling series; experiments/rec_nd_1d/run_gmm.sh:32-41 scaled as BASELINE C4) on this one GPU, a few steps
     # after the timed regions.  `value` stays the weak point above; this object is information.
     strong_n1 = None
-    if (world == 1 and rank == 0 and not emulated and not args.graph and not args.no_strong_n1 and args.workload == "c4"
-            and args.scaling == "weak" and not args.per_gpu):
+    if (args.full and world == 1 and rank == 0 and not emulated and not args.graph and not args.no_strong_n1
+            and args.workload == "c4" and args.scaling == "weak" and not args.per_gpu):
         try:
             big = strong_global
             big_level = gspec.resolve_act_level(big, device) if gspec is not None else 0
@@ -608,7 +659,7 @@ def run_worker(args) -> int:
                         with torch.no_grad():
                             issued[name] = kde_issued_atomics(prob, model.generator.sample(8192))
                     ops_pp = issued[name]
-                    peak = LDS_ATOMIC_U64_PER_CLK_CU * NUM_CU * CLOCK_GHZ            # G lane-atomics / s
+                    peak = LDS_U64_ATOMICS_PER_CLK_CU * NUM_CU * CLOCK_GHZ            # G lane-atomics / s
                     roof.update(bound="lds_atomic", unit="G ds_add_u64/s", peak=peak,
                                 peak_source="builder-measured: tools/ubench_lds_atomics2.hip, profiles/r02_ubench_lds_atomics2.txt "
                                             "(3.9 ds_add_u64 per clock and CU x 256 CUs x 2.4 GHz); not a guide number",
@@ -661,7 +712,7 @@ def run_worker(args) -> int:
         if world > 1 and ranks_seen != world:
             log(f"ERROR: the all-reduce saw {ranks_seen} ranks, expected {world}")
             rc = 3
-        if not args.no_cpu_baseline and world == 1 and not emulated:
+        if args.full and not args.no_cpu_baseline and world == 1 and not emulated:
             out["cpu_baseline"] = cpu_baseline(prob, args.cpu_budget)
             out["gpu_over_cpu"] = value / out["cpu_baseline"]["value"]
             out["cpu_baseline"]["parity"] = parity0

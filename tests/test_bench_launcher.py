@@ -120,7 +120,7 @@ def test_bench_two_ranks_share_gpu():
     two = torch.cuda.device_count() >= 2
     env = {} if two else {"MENTFLOW_SHARE_GPU": "1"}
     r = _run(["--gpus", "2", "--per-gpu", "65536", "--steps", "2", "--warmup", "1", "--repeats", "1", "--no-cpu-baseline",
-              "--meas-samples", "50000"], env=env, timeout=900)
+              "--meas-samples", "50000", "--full"], env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert j["n_gpus"] == 2 and j["ranks_seen"] == 2
@@ -137,6 +137,46 @@ def test_bench_graph_mode_small_batch():
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert j["n_gpus"] == 1 and "hipGraph" in j["config"]["step"] and j["config"]["global_batch"] == 25000
     assert 0.1 < j["ms_per_step"] < 5.0
+
+
+def test_plain_run_times_exactly_steps_and_dumps_reproducible_outputs(emu_library, tmp_path):
+    """A plain run: ONE timed region of --steps steps, none of the --full extras in the line, and --dump-outputs writes the
+    last timed step's outputs as float32 .npy files that the same arguments reproduce bit for bit."""
+    import numpy as np
+    lines = []
+    for tag in ("a", "b"):
+        r = _run(["--gpus", "1", "--per-gpu", "256", "--steps", "3", "--warmup", "1", "--meas-samples", "2000",
+                  "--test-emulator-lib", emu_library, "--dump-outputs", str(tmp_path / tag)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1]))
+    j = lines[0]
+    assert j["steps"] == 3 and j["timed_regions"]["count"] == 1 and j["timed_regions"]["steps_each"] == 3
+    assert abs(j["value"] - 256 * 3 / (j["ms_per_step"] * 3e-3)) < 1e-6 * j["value"]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in j
+    assert not {"roofline", "kernel_rooflines", "cpu_baseline", "strong_n1"} & set(j)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["discrepancy.npy", "entropy.npy", "gradients.npy", "loss.npy", "parameters.npy"]
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float32 and np.isfinite(a).all() and np.array_equal(a, b), n
+    assert np.load(tmp_path / "a" / "discrepancy.npy").shape == (100,)
+    assert abs(float(np.load(tmp_path / "a" / "loss.npy")) - j["config"]["final_loss"]) < 1e-6 * abs(j["config"]["final_loss"])
+    p, g = np.load(tmp_path / "a" / "parameters.npy"), np.load(tmp_path / "a" / "gradients.npy")
+    assert p.shape == g.shape and np.abs(g).max() > 0
+
+
+@pytest.mark.gpu
+def test_bench_full_carries_the_extras():
+    """`--full` on one GPU: the parity gate against the fp64 oracle passes, and the line carries the rooflines, the per-kernel
+    times and the CPU baseline next to the same headline fields a plain run prints."""
+    r = _run(["--workload", "c3", "--per-gpu", "65536", "--steps", "2", "--warmup", "1", "--repeats", "2", "--meas-samples",
+              "50000", "--cpu-budget", "2", "--full"], timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert j["value"] > 0 and j["timed_regions"]["count"] == 2
+    assert j["roofline"]["kernel"].startswith("flow_layer") and j["kernel_ms_per_step"] and j["kernel_rooflines"]
+    assert j["cpu_baseline"]["value"] > 0 and j["cpu_baseline"]["parity"]["ok"]
 
 
 def test_torchrun_launched_ranks_on_the_emulator(emu_library):

@@ -9,6 +9,6 @@ FLAGS="$1"; shift
 cd "$(dirname "$0")/.."
 VARIANT_TU=${AB_TU:-flow_bwd_fused_s0} tools/build_variant.sh _ab $FLAGS > /dev/null
 cp variants/_ab.so mentflow_amd/csrc/libmentflow_hip.so
-env "$@" python bench.py --steps 4 --warmup 1 --no-cpu-baseline 2>/dev/null | python -c "
+env "$@" python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 j=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$FLAGS $*', round(j['ms_per_step'],2), {k:round(v,2) for k,v in j['kernel_ms_per_step'].items()})"

@@ -10,7 +10,7 @@ if [ "${AB_TESTS:-1}" = "1" ]; then
   echo "== $(tail -1 $OUT/pytest.txt)"
 fi
 for lv in ${@:-0 1 2}; do
-  MENTFLOW_ACT_LEVEL=$lv timeout -k 10 300 python bench.py $BARGS > $OUT/level$lv.json 2> $OUT/level$lv.err || { echo "== level $lv: bench failed"; tail -5 $OUT/level$lv.err; exit 1; }
+  MENTFLOW_ACT_LEVEL=$lv timeout -k 10 300 python bench.py --full $BARGS > $OUT/level$lv.json 2> $OUT/level$lv.err || { echo "== level $lv: bench failed"; tail -5 $OUT/level$lv.err; exit 1; }
   python - $lv <<'PY'
 import json, sys
 lv = sys.argv[1]

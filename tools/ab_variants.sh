@@ -14,7 +14,7 @@ for v in "$@"; do
     fi
     echo "== $v: $(tail -1 $OUT/$v.pytest.txt)"
   fi
-  timeout -k 10 300 python bench.py $BARGS > $OUT/$v.json 2> $OUT/$v.err || { echo "== $v: bench failed"; tail -5 $OUT/$v.err; continue; }
+  timeout -k 10 300 python bench.py --full $BARGS > $OUT/$v.json 2> $OUT/$v.err || { echo "== $v: bench failed"; tail -5 $OUT/$v.err; continue; }
   python - "$v" <<'PY'
 import json, sys
 v = sys.argv[1]

@@ -6,7 +6,7 @@ cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/batch_sweep.txt; : > $OUT
 for n in 25000 100000 400000 1048576 2097152 4194304 8388608 16777216; do
   steps=10; [ $n -ge 8388608 ] && steps=5
-  python3 bench.py --per-gpu $n --steps $steps --warmup 3 --repeats 3 --no-cpu-baseline 2> gpurun_out/batch_sweep.err | python3 -c "
+  python3 bench.py --full --per-gpu $n --steps $steps --warmup 3 --repeats 3 --no-cpu-baseline 2> "${OUT%.txt}.err" | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=d['kernel_ms_per_step']

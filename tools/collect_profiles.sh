@@ -23,9 +23,10 @@ finish() {
   rm -rf $OUT
 }
 COMMIT=${2:-unknown}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 if part pmc; then
 cd /tmp && export TMPDIR=/tmp
-BENCH="python3 $GRAFT_REPO_ROOT/bench.py --steps 5 --warmup 2 --repeats 1 --no-cpu-baseline --no-strong-n1"
+BENCH="python3 $REPO/bench.py --full --steps 5 --warmup 2 --repeats 1 --no-cpu-baseline --no-strong-n1"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- $BENCH > $OUT/stats/bench.json 2> $OUT/stats/err.txt
 echo "stats done"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -- $BENCH > /dev/null 2> $OUT/fetch/err.txt
@@ -36,22 +37,22 @@ rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_C
 echo "sq done"; touch $OUT/fetch_done
 # C5 (2-D KDE dominant after the flow): kernel stats + SQ counters
 mkdir -p $OUT/c5_stats $OUT/c5_sq
-BENCH5="python3 $GRAFT_REPO_ROOT/bench.py --workload c5 --steps 5 --warmup 2 --repeats 1 --no-cpu-baseline"
+BENCH5="python3 $REPO/bench.py --full --workload c5 --steps 5 --warmup 2 --repeats 1 --no-cpu-baseline"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/c5_stats -- $BENCH5 > $OUT/c5_stats/bench.json 2> $OUT/c5_stats/err.txt
 echo "c5 stats done"
 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_ANY SQ_LDS_BANK_CONFLICT SQ_INSTS_LDS --output-format csv -d $OUT/c5_sq -- $BENCH5 > /dev/null 2> $OUT/c5_sq/err.txt
 echo "c5 sq done"
 fi
 if part benches; then
-cd $GRAFT_REPO_ROOT && python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
-python3 bench.py --scaling strong --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_strong_n1.json 2> $OUT/bench_strong_n1.err
-python3 bench.py --workload c5 --steps 10 --warmup 3 --no-cpu-baseline > $OUT/bench_c5.json 2> $OUT/bench_c5.err
-MENTFLOW_SHARE_GPU=1 python3 bench.py --gpus 2 --steps 5 --warmup 2 --repeats 1 --no-cpu-baseline 2> $OUT/bench_2ranks_shared.err | grep "^{" > $OUT/bench_2ranks_shared.json
+cd "$REPO" && python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
+python3 bench.py --full --scaling strong --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_strong_n1.json 2> $OUT/bench_strong_n1.err
+python3 bench.py --full --workload c5 --steps 10 --warmup 3 --no-cpu-baseline > $OUT/bench_c5.json 2> $OUT/bench_c5.err
+MENTFLOW_SHARE_GPU=1 python3 bench.py --full --gpus 2 --steps 5 --warmup 2 --repeats 1 --no-cpu-baseline 2> $OUT/bench_2ranks_shared.err | grep "^{" > $OUT/bench_2ranks_shared.json
 for w in c1 c2 c3; do
-  python3 bench.py --workload $w --steps 10 --warmup 3 --no-cpu-baseline > $OUT/bench_$w.json 2> $OUT/bench_$w.err
+  python3 bench.py --full --workload $w --steps 10 --warmup 3 --no-cpu-baseline > $OUT/bench_$w.json 2> $OUT/bench_$w.err
 done
-python3 bench.py --workload c3 --per-gpu 25000 --steps 50 --warmup 5 --no-cpu-baseline --meas-samples 200000 > $OUT/bench_c3_25k_eager.json 2> $OUT/bench_c3_25k_eager.err
-python3 bench.py --workload c3 --per-gpu 25000 --steps 50 --warmup 5 --no-cpu-baseline --meas-samples 200000 --graph --fused-adamw > $OUT/bench_c3_25k_graph_fused.json 2> $OUT/bench_c3_25k_graph_fused.err
+python3 bench.py --full --workload c3 --per-gpu 25000 --steps 50 --warmup 5 --no-cpu-baseline --meas-samples 200000 > $OUT/bench_c3_25k_eager.json 2> $OUT/bench_c3_25k_eager.err
+python3 bench.py --full --workload c3 --per-gpu 25000 --steps 50 --warmup 5 --no-cpu-baseline --meas-samples 200000 --graph --fused-adamw > $OUT/bench_c3_25k_graph_fused.json 2> $OUT/bench_c3_25k_graph_fused.err
 echo "other workloads done"
 fi
 if part stamps; then
@@ -65,7 +66,7 @@ for abl in NO_BARRIER NO_DW NO_SPLINE; do
 done
 # the hand-off levels side by side (one bench line each) and the batch sweep of the strong-scaling series
 for lv in 0 1 2; do
-  MENTFLOW_ACT_LEVEL=$lv python3 bench.py --steps 20 --warmup 3 --repeats 3 --no-cpu-baseline --no-strong-n1 > $OUT/bench_level$lv.json 2> $OUT/bench_level$lv.err
+  MENTFLOW_ACT_LEVEL=$lv python3 bench.py --full --steps 20 --warmup 3 --repeats 3 --no-cpu-baseline --no-strong-n1 > $OUT/bench_level$lv.json 2> $OUT/bench_level$lv.err
 done
 echo "stamps done"
 fi

@@ -77,7 +77,7 @@ if fetch and write:
             fh.write("%s,%d,%.1f,%.1f,%.0f\n" % r)
     # provenance: bench.py reports these numbers only for the workload / batch / backward variant that was profiled
     meta = {"workload": "c4", "per_gpu": 2097152, "fused_bwd": True, "tag": tag,
-            "command": "python3 bench.py --steps 5 --warmup 2 --repeats 1 --no-cpu-baseline"}
+            "command": "python3 bench.py --full --steps 5 --warmup 2 --repeats 1 --no-cpu-baseline --no-strong-n1"}
     try:      # the activation hand-off level the profiled bench ran at (bench.py echoes it in its line)
         bj = json.loads(open(os.path.join(src, "stats", "bench.json")).read().strip().splitlines()[-1])
         meta["act_level"] = int(bj["config"]["activation_handoff"]["level"])
