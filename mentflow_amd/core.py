@@ -117,7 +117,8 @@ class MENTFlow(nn.Module):
                 pos += 1
         plan = []
         for diagnostic, pre, slots, rows in groups.values():
-            if not diagnostic.kde or (diagnostic.noise and diagnostic.noise_scale > 0.0):
+            # hard bins, measurement noise and non-uniform edges (dense sums in raw_sums) take the generic loop
+            if not diagnostic.kde or not diagnostic.uniform or (diagnostic.noise and diagnostic.noise_scale > 0.0):
                 return None
             stacked = [torch.stack([r[k] for r in rows]).to(torch.float32).contiguous() for k in range(len(rows[0]))]
             meas = torch.stack([self.measurements[i][j] for (i, j) in slots]).to(torch.float32)

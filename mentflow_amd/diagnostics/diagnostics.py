@@ -7,12 +7,70 @@ projections of a measurement set into a single fused kernel launch (``Histogram*
 """
 from __future__ import annotations
 
+import logging
 from typing import Iterable, List, Optional, Sequence, Tuple, Union
 
 import torch
+from torch.utils.checkpoint import checkpoint
 
 from .. import ops
 from ..utils import coords_from_edges
+
+log = logging.getLogger("mentflow_amd.diagnostics")
+
+# An axis is UNIFORM when every bin centre lies within UNIFORM_TOL bin widths of the straight line through its first and
+# last centres (fp64).  Why 2e-3 bin widths:
+# - it is the size of fp32 rounding: an fp32 linspace stores its edges to half an ulp, 2^-24 |c| / delta bin widths (0 for
+#   64 bins on [997, 1003], whose step is a binary fraction; 6.7e-4 for 85 bins on [996.7, 1003.1]); the reference itself
+#   forms (u - c_k) / sigma in fp32 with that error, so the tolerance admits grids up to |c| / delta ~ 3e4.
+# - within it the kernels stay at that accuracy (kde.hip): the centre weight and its two neighbours are read from the table;
+#   the factorised tail |j| >= 2 puts bin kc + j at c_kc + j (c1 - c0), off by <= (2 j + 2) e bin widths (c1 - c0 is off
+#   the line's step by <= 2 e); the centre bin rint((u - c0) / (c1 - c0)) may drift by a few hundredths of a bin across
+#   the grid, which only moves the window by one bin for u near a midpoint, where it still reaches R + 1/2 - drift bins
+#   (ops.kde_radius truncates at ~9 sigma).
+# - a graded grid sits whole bins off its line (the two probes of tests/test_kde_launch_paths.py: 8.3 and 1.2) and
+#   is evaluated densely by raw_sums, as marginal_pdf / joint_pdf do.
+UNIFORM_TOL = 2.0e-3
+
+
+def is_uniform_axis(edges: torch.Tensor, tol: float = UNIFORM_TOL) -> bool:
+    c = coords_from_edges(edges.detach().to("cpu", torch.float64))
+    if c.numel() < 2:
+        return True
+    step = (c[-1] - c[0]) / (c.numel() - 1)
+    if not float(step) > 0.0:
+        return False
+    line = c[0] + step * torch.arange(c.numel(), dtype=torch.float64)
+    return float((c - line).abs().max() / step) <= tol
+
+
+# particles x projections x bins per dense chunk (16 M floats: 64 MiB per kernel matrix)
+_DENSE_CHUNK_ELEMS = 1 << 24
+
+
+def _gauss(u: torch.Tensor, c: torch.Tensor, sigma: float) -> torch.Tensor:
+    """[n, P, B] = exp(-((u[n, P] - c[B]) / sigma)^2 / 2)   (histogram.py:37-38)."""
+    return torch.exp(-0.5 * ((u[:, :, None] - c[None, None, :]) / sigma) ** 2)
+
+
+def _dense_chunk_1d(x, V, c, sigma):
+    return _gauss(x @ V.T, c, sigma).sum(0)
+
+
+def _dense_chunk_2d(x, V0, V1, cx, cy, sx, sy):
+    return torch.einsum("npa,npb->pab", _gauss(x @ V0.T, cx, sx), _gauss(x @ V1.T, cy, sy))
+
+
+def _dense_sums(fn, x: torch.Tensor, per_particle: int, *args) -> torch.Tensor:
+    """sum over particle chunks of fn(x_chunk, *args): each chunk is recomputed in the backward (checkpoint), so neither
+    pass holds more than one chunk's kernel matrix."""
+    chunk = max(1, _DENSE_CHUNK_ELEMS // max(1, per_particle))
+    total = None
+    for a in range(0, x.shape[0], chunk):
+        xc = x[a:a + chunk]
+        part = checkpoint(fn, xc, *args, use_reentrant=False) if xc.requires_grad else fn(xc, *args)
+        total = part if total is None else total + part
+    return total
 
 
 class Diagnostic(torch.nn.Module):
@@ -65,6 +123,14 @@ class Histogram(Diagnostic):
     def from_sums(self, S: torch.Tensor, n_total: int) -> torch.Tensor:
         raise NotImplementedError
 
+    uniform = True              # every axis on a uniform grid: the KDE kernels apply (set by the subclasses)
+
+    def _log_dense(self) -> None:
+        if not getattr(self, "_dense_logged", False):
+            self._dense_logged = True
+            log.info("%s: non-uniform bin edges, KDE sums evaluated densely in torch (the KDE kernels need a uniform grid)",
+                     type(self).__name__)
+
     def identity_rows(self, x: torch.Tensor) -> List[torch.Tensor]:
         eye = torch.eye(x.shape[1], dtype=x.dtype, device=x.device)
         return [r[None, :] for r in self.projection_rows(eye)]
@@ -100,6 +166,9 @@ class Histogram1D(Histogram):
         # step stays capturable into a hipGraph)
         self.resolution_value = float(self.resolution)
         self.bandwidth_value = float(self.bandwidth)
+        # non-uniform edges: dense KDE sums, normalised with coords[1] - coords[0] as marginal_pdf does (histogram.py:40)
+        self.uniform = is_uniform_axis(edges)
+        self.cell_value = self.resolution_value if self.uniform else float(self.coords[1] - self.coords[0])
 
     def projection_rows(self, matrix: torch.Tensor) -> List[torch.Tensor]:
         """u[:, axis] = x . matrix[axis]  (or  (x @ M.T) . direction = x . (direction @ M))."""
@@ -109,13 +178,17 @@ class Histogram1D(Histogram):
 
     def raw_sums(self, x: torch.Tensor, rows: List[torch.Tensor]) -> torch.Tensor:
         V = rows[0].to(torch.float32).contiguous()
+        if self.kde and not self.uniform:
+            self._log_dense()
+            return _dense_sums(_dense_chunk_1d, x, V.shape[0] * self.coords.numel(), V.to(x), self.coords.to(x),
+                               self.bandwidth_value)
         if self.kde:
             return ops.ProjKde1dFn.apply(x, V, self.coords, self.bandwidth_value, ops.kde_radius(self.bandwidth_bins))
         return ops.proj_hist_counts_1d(x.detach(), V, self.edges).to(torch.float32)
 
     def from_sums(self, S: torch.Tensor, n_total: int) -> torch.Tensor:
         if self.kde:
-            ghat, _ = ops.HistNormDiscFn.apply(S, None, True, 1.0 / n_total, self.resolution_value, 1.0e-10, 0, 0.0, 1.0)
+            ghat, _ = ops.HistNormDiscFn.apply(S, None, True, 1.0 / n_total, self.cell_value, 1.0e-10, 0, 0.0, 1.0)
             return ghat
         widths = (self.edges[1:] - self.edges[:-1])[None, :]
         return S / S.sum(dim=1, keepdim=True) / widths                    # torch.histogram(density=True)
@@ -144,6 +217,10 @@ class Histogram2D(Histogram):
         self.register_buffer("bandwidth_y", by * self.resolution_y)
         self.resolution_values = (float(self.resolution_x), float(self.resolution_y))
         self.bandwidth_values = (float(self.bandwidth_x), float(self.bandwidth_y))
+        # one non-uniform axis makes the whole image dense; joint_pdf normalises with the coords steps (histogram.py:70)
+        self.uniform = is_uniform_axis(self.edges_x) and is_uniform_axis(self.edges_y)
+        self.cell_value = (self.resolution_values[0] * self.resolution_values[1] if self.uniform else
+                           float(self.coords_x[1] - self.coords_x[0]) * float(self.coords_y[1] - self.coords_y[0]))
 
     @property
     def edges(self) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -155,6 +232,11 @@ class Histogram2D(Histogram):
     def raw_sums(self, x: torch.Tensor, rows: List[torch.Tensor]) -> torch.Tensor:
         V0 = rows[0].to(torch.float32).contiguous()
         V1 = rows[1].to(torch.float32).contiguous()
+        if self.kde and not self.uniform:
+            self._log_dense()
+            return _dense_sums(_dense_chunk_2d, x, V0.shape[0] * (self.coords_x.numel() + self.coords_y.numel()
+                                                                  + self.coords_x.numel() * self.coords_y.numel()),
+                               V0.to(x), V1.to(x), self.coords_x.to(x), self.coords_y.to(x), *self.bandwidth_values)
         if self.kde:
             return ops.ProjKde2dFn.apply(x, V0, V1, self.coords_x, self.coords_y, self.bandwidth_values[0],
                                          self.bandwidth_values[1], ops.kde_radius(self.bandwidth_bins[0]),
@@ -165,7 +247,7 @@ class Histogram2D(Histogram):
         if self.kde:
             P, Bx, By = S.shape
             ghat, _ = ops.HistNormDiscFn.apply(S.reshape(P, Bx * By), None, True, 1.0,
-                                               self.resolution_values[0] * self.resolution_values[1], 1.0e-10, 0, 0.0, 1.0)
+                                               self.cell_value, 1.0e-10, 0, 0.0, 1.0)
             return ghat.view(P, Bx, By)
         area = (self.edges_x[1:] - self.edges_x[:-1])[:, None] * (self.edges_y[1:] - self.edges_y[:-1])[None, :]
         return S / S.sum(dim=(1, 2), keepdim=True) / area[None]             # np.histogramdd(density=True)
