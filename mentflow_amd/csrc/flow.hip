@@ -128,9 +128,7 @@ static int rqs_layer_fwd_impl(const float* image, int d, int hidden_layers, int 
     // Workgroup size: 1024 threads (4 waves per SIMD at <= 128 VGPRs) for big batches; small batches (the reference's
     // 25 000 particles = 782 tiles) use fewer waves per workgroup so that the tiles spread over all 256 CUs.
     const int64_t nt = (n + 31) / 32;
-    static const int fwd_block_env = [] { const char* e = getenv("MENTFLOW_FWD_BLOCK"); return e ? atoi(e) : 0; }();
-    const int fwd_block = fwd_block_env ? fwd_block_env : (nt <= 4 * NUM_CU ? 256 : (nt <= 8 * NUM_CU ? 512 : 1024));
-    if (fwd_block != 256 && fwd_block != 512 && fwd_block != 1024) return fail("MENTFLOW_FWD_BLOCK must be 256, 512 or 1024");
+    const int fwd_block = nt <= 4 * NUM_CU ? 256 : (nt <= 8 * NUM_CU ? 512 : 1024);
     ProfScope prof(PK_FLOW_FWD, stream);
     if (launch_rqs_fwd(bins, hidden_layers, fwd_block, flow_grid(n, fwd_block / 64), smem, stream, image, d, x, n, y, logp_in,
                        logp_out, init_logp, sp, act, level))
@@ -150,10 +148,9 @@ static int fused_grid(int64_t n) {
     return (int)(ngroups > cap ? cap : (ngroups < 1 ? 1 : ngroups));
 }
 static int outer_accum_grid(int64_t n) {
-    static const int oa_mult = [] { const char* e = getenv("MENTFLOW_OA_MULT"); return e ? atoi(e) : 2; }();
     const int64_t ntiles = (n + 31) / 32;
     int64_t G = (ntiles + 7) / 8;                    // at least 8 tiles of work per workgroup
-    if (G > oa_mult * NUM_CU) G = oa_mult * NUM_CU;
+    if (G > 2 * NUM_CU) G = 2 * NUM_CU;
     if (G < 1) G = 1;
     return (int)G;
 }
@@ -213,9 +210,8 @@ extern "C" int mf_flow_rqs_layer_bwd(const float* image, int d, int hidden_layer
     }
     const size_t smem = sizeof(float) * (size_t)image_layout(d, hidden_layers, d).total;
     const int64_t ntb = (n + 31) / 32;
-    static const int bwd_block_env = [] { const char* e = getenv("MENTFLOW_BWD_BLOCK"); return e ? atoi(e) : 0; }();
     // small batches: one tile per SIMD on as many CUs as possible
-    const int bwd_block = bwd_block_env == 256 || bwd_block_env == 512 ? bwd_block_env : (ntb <= 4 * NUM_CU ? 256 : 512);
+    const int bwd_block = ntb <= 4 * NUM_CU ? 256 : 512;
     {
         ProfScope prof(PK_FLOW_BWD, stream);
         if (launch_rqs_bwd2(bins, hidden_layers, bwd_block, flow_grid(n, bwd_block / 64), smem, stream, image, d, x, n, gy, glogp,

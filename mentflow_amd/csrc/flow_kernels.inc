@@ -254,7 +254,7 @@ __device__ __forceinline__ float soft_clip_grad(float v, float a) {
 // spline).  v_permlane32_swap vdst, vsrc swaps lanes 32..63 of vdst with lanes 0..31 of vsrc; with the same value in
 // both operands vdst becomes {lo, lo} and vsrc {hi, hi}.
 __device__ __forceinline__ void half_pair(float v, int hh, float& lo, float& hi) {
-#if defined(MF_EMU) || defined(MF_NO_PERMLANE)
+#ifdef MF_EMU
     const float o = __shfl_xor(v, 32);
     lo = hh ? o : v;
     hi = hh ? v : o;
@@ -267,7 +267,7 @@ __device__ __forceinline__ void half_pair(float v, int hh, float& lo, float& hi)
 #endif
 }
 __device__ __forceinline__ void half_pair(int v, int hh, int& lo, int& hi) {
-#if defined(MF_EMU) || defined(MF_NO_PERMLANE)
+#ifdef MF_EMU
     const int o = __shfl_xor(v, 32);
     lo = hh ? o : v;
     hi = hh ? v : o;
@@ -577,8 +577,8 @@ typedef float act_f4 __attribute__((ext_vector_type(4)));
 typedef float act_f2 __attribute__((ext_vector_type(2)));
 // Written once, read once, 18 GB per step at C4: non-temporal accesses (global_store / global_load ... nt) keep the stream out of
 // the caches' way.  Measured at C4, level 2: plain 21.62-21.70 ms per step, nt stores 21.40 (forward 5.19 -> 4.99 ms), nt
-// stores + loads 21.36.  -DMF_ACT_PLAIN builds the plain form for A/B runs; the emulator has neither.
-#if defined(MF_EMU) || defined(MF_ACT_PLAIN)
+// stores + loads 21.36.  The emulator has neither.
+#ifdef MF_EMU
 #define MF_ACT_ST(p, v) (*(p) = (v))
 #define MF_ACT_LD(p) (*(p))
 #else
@@ -849,55 +849,33 @@ __device__ __forceinline__ unsigned lds_addr(const float* p) { return (unsigned)
 
 // group g: request the fragments of the group starting at k-step S4N into n[] (unconditionally: a skipped group's
 // fragments are never used), multiply-accumulate the four k-steps held in a[].
-// BA: the B operands (activations) are taken from AGPRs.  An MFMA reads A / B / C from either register file; an operand
-// constraint "v" on values that live across the VALU-heavy spline makes the compiler shuttle them between the files
-// (v_accvgpr_write to park, v_accvgpr_read to bring back: 64 VALU per 32-row tile and use), "a" lets them stay parked.
-#define MF_DEF_MFMA4(SUF, BC)                                                                                         \
-    template <int KS, int S4N>                                                                                        \
-    __device__ __forceinline__ void mfma4_pf_##SUF(f32x16_t& acc, const float (&a)[4], float (&n)[4], unsigned addr,  \
-                                                   float b0, float b1, float b2, float b3) {                          \
-        asm volatile(                                                                                                 \
-            "ds_read_b32 %1, %9 offset:%14\n\t"                                                                       \
-            "ds_read_b32 %2, %9 offset:%15\n\t"                                                                       \
-            "ds_read_b32 %3, %9 offset:%16\n\t"                                                                       \
-            "ds_read_b32 %4, %9 offset:%17\n\t"                                                                       \
-            "v_mfma_f32_32x32x2_f32 %0, %5, %10, %0\n\t"                                                              \
-            "v_mfma_f32_32x32x2_f32 %0, %6, %11, %0\n\t"                                                              \
-            "v_mfma_f32_32x32x2_f32 %0, %7, %12, %0\n\t"                                                              \
-            "v_mfma_f32_32x32x2_f32 %0, %8, %13, %0\n\t"                                                              \
-            "s_waitcnt lgkmcnt(0)"                                                                                    \
-            : "+v"(acc), "=&v"(n[0]), "=&v"(n[1]), "=&v"(n[2]), "=&v"(n[3])                                           \
-            : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(addr), BC(b0), BC(b1), BC(b2), BC(b3),                  \
-              "n"(kcol(S4N) * KS * 4), "n"(kcol(S4N + 1) * KS * 4), "n"(kcol(S4N + 2) * KS * 4),                      \
-              "n"(kcol(S4N + 3) * KS * 4));                                                                           \
-    }                                                                                                                 \
-    /* last group of a chain: no prefetch */                                                                          \
-    __device__ __forceinline__ void mfma4_last_##SUF(f32x16_t& acc, const float (&a)[4], float b0, float b1, float b2, \
-                                                     float b3) {                                                      \
-        asm volatile(                                                                                                 \
-            "s_nop 1\n\t"                                                                                             \
-            "v_mfma_f32_32x32x2_f32 %0, %1, %5, %0\n\t"                                                               \
-            "v_mfma_f32_32x32x2_f32 %0, %2, %6, %0\n\t"                                                               \
-            "v_mfma_f32_32x32x2_f32 %0, %3, %7, %0\n\t"                                                               \
-            "v_mfma_f32_32x32x2_f32 %0, %4, %8, %0"                                                                   \
-            : "+v"(acc)                                                                                               \
-            : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), BC(b0), BC(b1), BC(b2), BC(b3));                            \
-    }
-#define MF_BC_V(x) "v"(x)
-#define MF_BC_A(x) "a"(x)
-MF_DEF_MFMA4(v, MF_BC_V)
-MF_DEF_MFMA4(a, MF_BC_A)
-#undef MF_DEF_MFMA4
-template <int KS, int S4N, bool BA = false>
+template <int KS, int S4N>
 __device__ __forceinline__ void mfma4_pf(f32x16_t& acc, const float (&a)[4], float (&n)[4], unsigned addr, float b0, float b1,
                                          float b2, float b3) {
-    if constexpr (BA) mfma4_pf_a<KS, S4N>(acc, a, n, addr, b0, b1, b2, b3);
-    else mfma4_pf_v<KS, S4N>(acc, a, n, addr, b0, b1, b2, b3);
+    asm volatile(
+        "ds_read_b32 %1, %9 offset:%14\n\t"
+        "ds_read_b32 %2, %9 offset:%15\n\t"
+        "ds_read_b32 %3, %9 offset:%16\n\t"
+        "ds_read_b32 %4, %9 offset:%17\n\t"
+        "v_mfma_f32_32x32x2_f32 %0, %5, %10, %0\n\t"
+        "v_mfma_f32_32x32x2_f32 %0, %6, %11, %0\n\t"
+        "v_mfma_f32_32x32x2_f32 %0, %7, %12, %0\n\t"
+        "v_mfma_f32_32x32x2_f32 %0, %8, %13, %0\n\t"
+        "s_waitcnt lgkmcnt(0)"
+        : "+v"(acc), "=&v"(n[0]), "=&v"(n[1]), "=&v"(n[2]), "=&v"(n[3])
+        : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(addr), "v"(b0), "v"(b1), "v"(b2), "v"(b3),
+          "n"(kcol(S4N) * KS * 4), "n"(kcol(S4N + 1) * KS * 4), "n"(kcol(S4N + 2) * KS * 4), "n"(kcol(S4N + 3) * KS * 4));
 }
-template <bool BA = false>
+// last group of a chain: no prefetch
 __device__ __forceinline__ void mfma4_last(f32x16_t& acc, const float (&a)[4], float b0, float b1, float b2, float b3) {
-    if constexpr (BA) mfma4_last_a(acc, a, b0, b1, b2, b3);
-    else mfma4_last_v(acc, a, b0, b1, b2, b3);
+    asm volatile(
+        "s_nop 1\n\t"
+        "v_mfma_f32_32x32x2_f32 %0, %1, %5, %0\n\t"
+        "v_mfma_f32_32x32x2_f32 %0, %2, %6, %0\n\t"
+        "v_mfma_f32_32x32x2_f32 %0, %3, %7, %0\n\t"
+        "v_mfma_f32_32x32x2_f32 %0, %4, %8, %0"
+        : "+v"(acc)
+        : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(b0), "v"(b1), "v"(b2), "v"(b3));
 }
 // the compiler cannot see the MFMAs inside the blocks: pad the MFMA -> VALU read distance (18 wait states) by hand
 __device__ __forceinline__ void mfma_drain(f32x16_t& acc) { asm volatile("s_nop 15\n\ts_nop 3" : "+v"(acc)); }
@@ -906,19 +884,11 @@ __device__ __forceinline__ void mfma_drain(f32x16_t& acc) { asm volatile("s_nop 
 
 // B operand accessors of a chain: k-step S of an accumulator pair, or of a 32-slot vector
 struct BTile {
-    static constexpr bool agpr = false;
-    const f32x16_t (&t)[2];
-    template <int S>
-    __device__ __forceinline__ float get() const { return t[S >> 4][S & 15]; }
-};
-struct BTileA {                          // the same, operands constrained to AGPRs (long-lived activations)
-    static constexpr bool agpr = true;
     const f32x16_t (&t)[2];
     template <int S>
     __device__ __forceinline__ float get() const { return t[S >> 4][S & 15]; }
 };
 struct BVec {
-    static constexpr bool agpr = false;
     const float (&v)[32];
     template <int S>
     __device__ __forceinline__ float get() const { return v[S]; }
@@ -937,7 +907,7 @@ __device__ __forceinline__ void chain64(f32x16_t& acc, const float* wl, int g0, 
         _Pragma("unroll") for (int j = 0; j < 4; ++j) CUR[j] = wl[kcol(4 * G + j) * KS];                              \
     }                                                                                                                 \
     if (G >= g0 && G < g1)                                                                                            \
-        mfma4_pf<KS, (4 * G + 4) & 31, BOp::agpr>(acc, CUR, NXT, addr, b.template get<4 * G>(), b.template get<4 * G + 1>(), \
+        mfma4_pf<KS, (4 * G + 4) & 31>(acc, CUR, NXT, addr, b.template get<4 * G>(), b.template get<4 * G + 1>(), \
                                        b.template get<4 * G + 2>(), b.template get<4 * G + 3>());
     MF_GRP(0, a0, a1) MF_GRP(1, a1, a0) MF_GRP(2, a0, a1) MF_GRP(3, a1, a0) MF_GRP(4, a0, a1) MF_GRP(5, a1, a0) MF_GRP(6, a0, a1)
 #undef MF_GRP
@@ -946,7 +916,7 @@ __device__ __forceinline__ void chain64(f32x16_t& acc, const float* wl, int g0, 
         for (int j = 0; j < 4; ++j) a1[j] = wl[kcol(28 + j) * KS];
     }
     if (7 >= g0 && 7 < g1)
-        mfma4_last<BOp::agpr>(acc, a1, b.template get<28>(), b.template get<29>(), b.template get<30>(), b.template get<31>());
+        mfma4_last(acc, a1, b.template get<28>(), b.template get<29>(), b.template get<30>(), b.template get<31>());
     mfma_drain(acc);
 #else
 #define MF_STEP(S) if ((S) >= 4 * g0 && (S) < 4 * g1) acc = mfma(wl[kcol(S) * KS], b.template get<S>(), acc);
@@ -976,7 +946,7 @@ __device__ __forceinline__ void chain64_30(f32x16_t& acc, const float* wl, const
     float a0[4], a1[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) a0[j] = wl[kcol(j) * KS];
-#define MF_G(G, CUR, NXT) mfma4_pf<KS, 4 * G + 4, BOp::agpr>(acc, CUR, NXT, addr, b.template get<4 * G>(), b.template get<4 * G + 1>(), \
+#define MF_G(G, CUR, NXT) mfma4_pf<KS, 4 * G + 4>(acc, CUR, NXT, addr, b.template get<4 * G>(), b.template get<4 * G + 1>(), \
                                                              b.template get<4 * G + 2>(), b.template get<4 * G + 3>());
     MF_G(0, a0, a1) MF_G(1, a1, a0) MF_G(2, a0, a1) MF_G(3, a1, a0) MF_G(4, a0, a1) MF_G(5, a1, a0) MF_G(6, a0, a1)
 #undef MF_G
@@ -996,10 +966,10 @@ __device__ __forceinline__ void chain64_30(f32x16_t& acc, const float* wl, const
 template <int KS, int G, int NEXT_S, class BOp>     // NEXT_S: first k-step of the group to prefetch, -1: none
 __device__ __forceinline__ void chain_grp(f32x16_t& acc, const float (&cur)[4], float (&nxt)[4], unsigned addr_next, const BOp& b) {
     if constexpr (NEXT_S >= 0)
-        mfma4_pf<KS, NEXT_S, BOp::agpr>(acc, cur, nxt, addr_next, b.template get<4 * G>(), b.template get<4 * G + 1>(),
+        mfma4_pf<KS, NEXT_S>(acc, cur, nxt, addr_next, b.template get<4 * G>(), b.template get<4 * G + 1>(),
                              b.template get<4 * G + 2>(), b.template get<4 * G + 3>());
     else
-        mfma4_last<BOp::agpr>(acc, cur, b.template get<4 * G>(), b.template get<4 * G + 1>(), b.template get<4 * G + 2>(),
+        mfma4_last(acc, cur, b.template get<4 * G>(), b.template get<4 * G + 1>(), b.template get<4 * G + 2>(),
                    b.template get<4 * G + 3>());
 }
 #endif
@@ -1034,62 +1004,53 @@ __device__ __forceinline__ void chain64x2r(f32x16_t& acc0, f32x16_t& acc1, const
     chain64<KS>(acc1, wl1, S1, E1, b);
 #endif
 }
-template <int KS, int NG, class BOp>
-__device__ __forceinline__ void chain64x2(f32x16_t& acc0, f32x16_t& acc1, const float* wl0, const float* wl1, const BOp& b) {
-    chain64x2r<KS, 0, NG, 0, NG>(acc0, acc1, wl0, wl1, b);
-}
 // Same pair, equal ranges [0, NG), with the MFMAs of the two chains INTERLEAVED (acc0, acc1, acc0, ...): consecutive
 // MFMAs are independent, which removes the ~3.5 cycles of issue stall a dependent fp32 MFMA pays
 // (tools/ubench_chain.hip: 64 MFMAs in 4445 instead of 4671 cycles).  Costs eight more fragment registers.
 #ifdef MF_ASM_CHAIN
-#define MF_DEF_MFMA8(SUF, BC)                                                                                         \
-    template <int KS, int S4N>                                                                                        \
-    __device__ __forceinline__ void mfma8_pf_##SUF(f32x16_t& acc0, f32x16_t& acc1, const float (&a)[8], float (&n)[8], \
-                                                   unsigned addr0, unsigned addr1, float b0, float b1, float b2,      \
-                                                   float b3) {                                                        \
-        asm volatile(                                                                                                 \
-            "ds_read_b32 %2, %18 offset:%24\n\t"                                                                      \
-            "ds_read_b32 %3, %18 offset:%25\n\t"                                                                      \
-            "ds_read_b32 %4, %18 offset:%26\n\t"                                                                      \
-            "ds_read_b32 %5, %18 offset:%27\n\t"                                                                      \
-            "ds_read_b32 %6, %19 offset:%24\n\t"                                                                      \
-            "ds_read_b32 %7, %19 offset:%25\n\t"                                                                      \
-            "ds_read_b32 %8, %19 offset:%26\n\t"                                                                      \
-            "ds_read_b32 %9, %19 offset:%27\n\t"                                                                      \
-            "v_mfma_f32_32x32x2_f32 %0, %10, %20, %0\n\t"                                                             \
-            "v_mfma_f32_32x32x2_f32 %1, %14, %20, %1\n\t"                                                             \
-            "v_mfma_f32_32x32x2_f32 %0, %11, %21, %0\n\t"                                                             \
-            "v_mfma_f32_32x32x2_f32 %1, %15, %21, %1\n\t"                                                             \
-            "v_mfma_f32_32x32x2_f32 %0, %12, %22, %0\n\t"                                                             \
-            "v_mfma_f32_32x32x2_f32 %1, %16, %22, %1\n\t"                                                             \
-            "v_mfma_f32_32x32x2_f32 %0, %13, %23, %0\n\t"                                                             \
-            "v_mfma_f32_32x32x2_f32 %1, %17, %23, %1\n\t"                                                             \
-            "s_waitcnt lgkmcnt(0)"                                                                                    \
-            : "+v"(acc0), "+v"(acc1), "=&v"(n[0]), "=&v"(n[1]), "=&v"(n[2]), "=&v"(n[3]), "=&v"(n[4]), "=&v"(n[5]),   \
-              "=&v"(n[6]), "=&v"(n[7])                                                                                \
-            : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(a[4]), "v"(a[5]), "v"(a[6]), "v"(a[7]), "v"(addr0),     \
-              "v"(addr1), BC(b0), BC(b1), BC(b2), BC(b3), "n"(kcol(S4N) * KS * 4), "n"(kcol(S4N + 1) * KS * 4),       \
-              "n"(kcol(S4N + 2) * KS * 4), "n"(kcol(S4N + 3) * KS * 4));                                              \
-    }                                                                                                                 \
-    __device__ __forceinline__ void mfma8_last_##SUF(f32x16_t& acc0, f32x16_t& acc1, const float (&a)[8], float b0,   \
-                                                     float b1, float b2, float b3) {                                  \
-        asm volatile(                                                                                                 \
-            "s_nop 1\n\t"                                                                                             \
-            "v_mfma_f32_32x32x2_f32 %0, %2, %10, %0\n\t"                                                              \
-            "v_mfma_f32_32x32x2_f32 %1, %6, %10, %1\n\t"                                                              \
-            "v_mfma_f32_32x32x2_f32 %0, %3, %11, %0\n\t"                                                              \
-            "v_mfma_f32_32x32x2_f32 %1, %7, %11, %1\n\t"                                                              \
-            "v_mfma_f32_32x32x2_f32 %0, %4, %12, %0\n\t"                                                              \
-            "v_mfma_f32_32x32x2_f32 %1, %8, %12, %1\n\t"                                                              \
-            "v_mfma_f32_32x32x2_f32 %0, %5, %13, %0\n\t"                                                              \
-            "v_mfma_f32_32x32x2_f32 %1, %9, %13, %1"                                                                  \
-            : "+v"(acc0), "+v"(acc1)                                                                                  \
-            : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(a[4]), "v"(a[5]), "v"(a[6]), "v"(a[7]), BC(b0), BC(b1), \
-              BC(b2), BC(b3));                                                                                        \
-    }
-MF_DEF_MFMA8(v, MF_BC_V)
-MF_DEF_MFMA8(a, MF_BC_A)
-#undef MF_DEF_MFMA8
+template <int KS, int S4N>
+__device__ __forceinline__ void mfma8_pf(f32x16_t& acc0, f32x16_t& acc1, const float (&a)[8], float (&n)[8], unsigned addr0,
+                                         unsigned addr1, float b0, float b1, float b2, float b3) {
+    asm volatile(
+        "ds_read_b32 %2, %18 offset:%24\n\t"
+        "ds_read_b32 %3, %18 offset:%25\n\t"
+        "ds_read_b32 %4, %18 offset:%26\n\t"
+        "ds_read_b32 %5, %18 offset:%27\n\t"
+        "ds_read_b32 %6, %19 offset:%24\n\t"
+        "ds_read_b32 %7, %19 offset:%25\n\t"
+        "ds_read_b32 %8, %19 offset:%26\n\t"
+        "ds_read_b32 %9, %19 offset:%27\n\t"
+        "v_mfma_f32_32x32x2_f32 %0, %10, %20, %0\n\t"
+        "v_mfma_f32_32x32x2_f32 %1, %14, %20, %1\n\t"
+        "v_mfma_f32_32x32x2_f32 %0, %11, %21, %0\n\t"
+        "v_mfma_f32_32x32x2_f32 %1, %15, %21, %1\n\t"
+        "v_mfma_f32_32x32x2_f32 %0, %12, %22, %0\n\t"
+        "v_mfma_f32_32x32x2_f32 %1, %16, %22, %1\n\t"
+        "v_mfma_f32_32x32x2_f32 %0, %13, %23, %0\n\t"
+        "v_mfma_f32_32x32x2_f32 %1, %17, %23, %1\n\t"
+        "s_waitcnt lgkmcnt(0)"
+        : "+v"(acc0), "+v"(acc1), "=&v"(n[0]), "=&v"(n[1]), "=&v"(n[2]), "=&v"(n[3]), "=&v"(n[4]), "=&v"(n[5]), "=&v"(n[6]),
+          "=&v"(n[7])
+        : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(a[4]), "v"(a[5]), "v"(a[6]), "v"(a[7]), "v"(addr0), "v"(addr1),
+          "v"(b0), "v"(b1), "v"(b2), "v"(b3), "n"(kcol(S4N) * KS * 4), "n"(kcol(S4N + 1) * KS * 4), "n"(kcol(S4N + 2) * KS * 4),
+          "n"(kcol(S4N + 3) * KS * 4));
+}
+__device__ __forceinline__ void mfma8_last(f32x16_t& acc0, f32x16_t& acc1, const float (&a)[8], float b0, float b1, float b2,
+                                           float b3) {
+    asm volatile(
+        "s_nop 1\n\t"
+        "v_mfma_f32_32x32x2_f32 %0, %2, %10, %0\n\t"
+        "v_mfma_f32_32x32x2_f32 %1, %6, %10, %1\n\t"
+        "v_mfma_f32_32x32x2_f32 %0, %3, %11, %0\n\t"
+        "v_mfma_f32_32x32x2_f32 %1, %7, %11, %1\n\t"
+        "v_mfma_f32_32x32x2_f32 %0, %4, %12, %0\n\t"
+        "v_mfma_f32_32x32x2_f32 %1, %8, %12, %1\n\t"
+        "v_mfma_f32_32x32x2_f32 %0, %5, %13, %0\n\t"
+        "v_mfma_f32_32x32x2_f32 %1, %9, %13, %1"
+        : "+v"(acc0), "+v"(acc1)
+        : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(a[4]), "v"(a[5]), "v"(a[6]), "v"(a[7]), "v"(b0), "v"(b1), "v"(b2),
+          "v"(b3));
+}
 // last group of a chain with only TWO k-steps left (the spline uses 30 of a lane half's 32 slots: the k-steps of the two
 // padding slots would multiply zeros)
 __device__ __forceinline__ void mfma8_half(f32x16_t& acc0, f32x16_t& acc1, const float (&a)[8], float b0, float b1) {
@@ -1101,18 +1062,6 @@ __device__ __forceinline__ void mfma8_half(f32x16_t& acc0, f32x16_t& acc1, const
         "v_mfma_f32_32x32x2_f32 %1, %5, %7, %1"
         : "+v"(acc0), "+v"(acc1)
         : "v"(a[0]), "v"(a[1]), "v"(a[4]), "v"(a[5]), "v"(b0), "v"(b1));
-}
-template <int KS, int S4N, bool BA = false>
-__device__ __forceinline__ void mfma8_pf(f32x16_t& acc0, f32x16_t& acc1, const float (&a)[8], float (&n)[8], unsigned addr0,
-                                         unsigned addr1, float b0, float b1, float b2, float b3) {
-    if constexpr (BA) mfma8_pf_a<KS, S4N>(acc0, acc1, a, n, addr0, addr1, b0, b1, b2, b3);
-    else mfma8_pf_v<KS, S4N>(acc0, acc1, a, n, addr0, addr1, b0, b1, b2, b3);
-}
-template <bool BA = false>
-__device__ __forceinline__ void mfma8_last(f32x16_t& acc0, f32x16_t& acc1, const float (&a)[8], float b0, float b1, float b2,
-                                           float b3) {
-    if constexpr (BA) mfma8_last_a(acc0, acc1, a, b0, b1, b2, b3);
-    else mfma8_last_v(acc0, acc1, a, b0, b1, b2, b3);
 }
 #endif
 // TAIL2: the last of the NG groups only has its first two k-steps (k-steps 4 NG - 2, 4 NG - 1 multiply padding)
@@ -1130,14 +1079,13 @@ __device__ __forceinline__ void chain64x2i(f32x16_t& acc0, f32x16_t& acc1, const
 #define MF_I(G, CUR, NXT)                                                                                             \
     if constexpr (G < NG) {                                                                                          \
         if constexpr (G + 1 < NG)                                                                                    \
-            mfma8_pf<KS, (4 * G + 4) & 31, BOp::agpr>(acc0, acc1, CUR, NXT, addr0, addr1, b.template get<4 * G>(),   \
+            mfma8_pf<KS, (4 * G + 4) & 31>(acc0, acc1, CUR, NXT, addr0, addr1, b.template get<4 * G>(),              \
                                            b.template get<4 * G + 1>(), b.template get<4 * G + 2>(),                 \
                                            b.template get<4 * G + 3>());                                             \
         else if constexpr (TAIL2)                                                                                    \
             mfma8_half(acc0, acc1, CUR, b.template get<4 * G>(), b.template get<4 * G + 1>());                       \
         else                                                                                                         \
-            mfma8_last<BOp::agpr>(acc0, acc1, CUR, b.template get<4 * G>(), b.template get<4 * G + 1>(),               \
-                                  b.template get<4 * G + 2>(),                                                       \
+            mfma8_last(acc0, acc1, CUR, b.template get<4 * G>(), b.template get<4 * G + 1>(), b.template get<4 * G + 2>(), \
                        b.template get<4 * G + 3>());                                                                 \
     }
     MF_I(0, a0, a1) MF_I(1, a1, a0) MF_I(2, a0, a1) MF_I(3, a1, a0) MF_I(4, a0, a1) MF_I(5, a1, a0) MF_I(6, a0, a1) MF_I(7, a1, a0)
@@ -1149,7 +1097,8 @@ __device__ __forceinline__ void chain64x2i(f32x16_t& acc0, f32x16_t& acc1, const
 #endif
 }
 
-// run-time number of groups (wave-uniform): ONE branch into straight-line instances
+// run-time number of groups (wave-uniform): ONE branch into straight-line instances.  (Per-group branches cost a lone wave
+// ~40 %; a single fall-through switch made the compiler copy the accumulators and the fragments at every label.)
 template <int KS, class BOp>
 __device__ __forceinline__ void chain64x2_upto(f32x16_t& acc0, f32x16_t& acc1, const float* wl0, const float* wl1, int ng,
                                                const BOp& b) {
@@ -1187,29 +1136,6 @@ __device__ __forceinline__ void input_layer4(const float* W0, const float* b0, i
         h[rt] = acc;
     }
     relu2(h);
-}
-
-// acc += sum over the k-step groups [0, g1) of A * B, g1 wave-uniform at run time, with ONE branch: a switch over g1
-// whose cases are separate straight-line chains with compile-time bounds.  (The eight per-group branches of
-// chain64(…, 0, g1, …) cost a lone wave ~40 % here; a single fall-through switch entered at group g1 - 1 made the
-// compiler copy the accumulator and the fragments at every label.)
-template <int KS, class BOp>
-__device__ __forceinline__ void chain64_upto(f32x16_t& acc, const float* wl, int g1, const BOp& b) {
-#ifdef MF_ASM_CHAIN
-    switch (g1) {
-        case 0: break;
-        case 1: chain64<KS>(acc, wl, 0, 1, b); break;
-        case 2: chain64<KS>(acc, wl, 0, 2, b); break;
-        case 3: chain64<KS>(acc, wl, 0, 3, b); break;
-        case 4: chain64<KS>(acc, wl, 0, 4, b); break;
-        case 5: chain64<KS>(acc, wl, 0, 5, b); break;
-        case 6: chain64<KS>(acc, wl, 0, 6, b); break;
-        case 7: chain64<KS>(acc, wl, 0, 7, b); break;
-        default: chain64<KS>(acc, wl, 0, 8, b); break;
-    }
-#else
-    chain64<KS>(acc, wl, 0, g1, b);
-#endif
 }
 
 // Diagnostic build only (-DMF_WS_DIAG): cycle stamps of pair 0 of every workgroup, read back with mf_debug_ws_read.
@@ -1362,8 +1288,7 @@ __device__ __forceinline__ void dw_mac(const DwFrag& f, bool mm, bool bias, f32x
 // acc += A[rows 32 ra ..][particles] * B[rows 32 rb ..][particles]^T over the staged tiles [t0, t0 + 2 npair);  bsum += row
 // sums of A over the tile pairs selected by bias_pair (-1: every pair; p: pair p only — the two waves that share a row
 // tile of a full product split its bias sums between them).  Two fragment sets ping-pong so that the reads of the next
-// tile are in flight during the MFMAs of this one.  (Compiler-scheduled form: the emulator build, and the gfx950 build
-// without MF_DW_ASM.)
+// tile are in flight during the MFMAs of this one.  (Compiler-scheduled form: the emulator build.)
 __device__ __forceinline__ void dw_accum(const float* SA, const float* SB, int ra, int rb, int t0, int npair, bool mm,
                                          int bias_pair, int lane, f32x16_t& acc, float& bsum) {
     const int i = lane & 31, kk = lane >> 5;
@@ -1383,7 +1308,7 @@ __device__ __forceinline__ void dw_accum(const float* SA, const float* SB, int r
     }
 }
 
-// ---- the same product, hand-scheduled (gfx950 build; -DMF_DW_COMPILER keeps the compiler-scheduled form for A/B) -------
+// ---- the same product, hand-scheduled (gfx950 build) ----------------------------------------------------------
 // The compiler's code for dw_accum costs a lone wave ~1.3 k cycles per product on top of its MFMAs (r02 ablation:
 // 40.8 k cycles for 26.6 k of matrix-pipe time): SLP-packed bias sums (v_pk_add_f32 fed by v_mov / v_accvgpr_read
 // shuffles) under exec-mask branches, address arithmetic per call, four waits per tile.  dw_product_asm.inc (generated by
@@ -1392,8 +1317,7 @@ __device__ __forceinline__ void dw_accum(const float* SA, const float* SB, int r
 // sums are plain v_add_f32, nothing branches, and the only operands are the accumulator and ONE address per matrix.
 // Fragment registers are fixed physical registers (clobbers): ds_read_b64 fills 2-register tuples whose single registers
 // the MFMAs name, which operand constraints cannot express.
-#if defined(MF_ASM_CHAIN) && !defined(MF_DW_COMPILER)
-#define MF_DW_ASM 1
+#ifdef MF_ASM_CHAIN
 #include "dw_product_asm.inc"
 // This wave's share of one stage's product.  full: block (fra, frb) of a 64 x 64 product over all four tiles, bias row sums
 // from tile pair frb (the two waves of a row tile split them); otherwise block (hra, 0) of a one-column-tile product over
@@ -1547,7 +1471,7 @@ __global__ __launch_bounds__(FB_BLOCK) void rqs_layer_bwd_fused_kernel(const flo
     // product roles of this wave
     const int fra = wid >> 1, frb = wid & 1;              // full 64 x 64 product
     const int hra = wid & 1, ht0 = 2 * (wid >> 1);        // single column tile, k split over tile pairs
-#ifdef MF_DW_ASM
+#ifdef MF_ASM_CHAIN
     const DwRole role{fra, frb, hra, ht0};
 #endif
 
@@ -1790,7 +1714,7 @@ __global__ __launch_bounds__(FB_BLOCK) void rqs_layer_bwd_fused_kernel(const flo
             {
                 const bool full = rt1_i != 0;
                 const bool mm = kend3_i > 0;
-#if defined(MF_DW_ASM) && !defined(MF_FB_NO_DW)
+#if defined(MF_ASM_CHAIN) && !defined(MF_FB_NO_DW)
                 dw_product_stage(SA, SB, role, full, mm, lane, accF, bsF);
 #else
                 FB_DW(SA, SB, full ? fra : hra, full ? frb : 0, full ? 0 : ht0, full ? 2 : 1, mm, full ? frb : -1, lane, accF, bsF);
@@ -1878,7 +1802,7 @@ __global__ __launch_bounds__(FB_BLOCK) void rqs_layer_bwd_fused_kernel(const flo
             FB_SYNC();
             WS_ACC(c_[12], t1_);
             t1_ = WS_T();
-#if defined(MF_DW_ASM) && !defined(MF_FB_NO_DW)
+#if defined(MF_ASM_CHAIN) && !defined(MF_FB_NO_DW)
             dw_product_stage(SA, SB, role, true, !(fra == 0 && frb == 1 && sp.kend_h[0] <= 16), lane, accT[l], bsT[l]);
 #else
             FB_DW(SA, SB, fra, frb, 0, 2, !(fra == 0 && frb == 1 && sp.kend_h[0] <= 16), frb, lane, accT[l], bsT[l]);
@@ -1895,7 +1819,7 @@ __global__ __launch_bounds__(FB_BLOCK) void rqs_layer_bwd_fused_kernel(const flo
         relu_mask_stage(gh, h[0], myA, lane);
         stage_x_rows(myB, col, hh, d, xr);                  // S_B rows 0..d-1 <- x (rows >= d: stale finite values, never flushed)
         FB_SYNC();
-#if defined(MF_DW_ASM) && !defined(MF_FB_NO_DW)
+#if defined(MF_ASM_CHAIN) && !defined(MF_FB_NO_DW)
         dw_product_stage(SA, SB, role, false, true, lane, accT[0], bsT[0]);
 #else
         FB_DW(SA, SB, hra, 0, ht0, 1, true, -1, lane, accT[0], bsT[0]);

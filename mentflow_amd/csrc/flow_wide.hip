@@ -174,7 +174,6 @@ __device__ __forceinline__ void frag2_mfma(f32x16_t& acc, const Frag2& f, const 
 // (up to 2 048 cycles of matrix pipe against an L2 round trip that exceeds the 1 024 cycles of a single block when 256 CUs read
 // the same image), across the output tiles of a layer — the mask bounds are wave-uniform, so "the next active pair" is known when
 // the current one starts; the second block of a pair is fetched even when the masks switch its MFMAs off (zeros, never used).
-// -DMF_WIDE_NO_PREFETCH builds the plain form (A/B runs).
 template <class B>
 __device__ __forceinline__ void wide_block(f32x16_t& acc, gfp blk, int lane, const B& b) {
     Frag f;
@@ -236,21 +235,6 @@ template <bool PAIR>
 __device__ __forceinline__ void wide_hidden(gfp H, const f32x16_t (&in)[WIDE_HT], f32x16_t (&out)[WIDE_HT],
                                             int lane, int hh, const WideSp& sp) {
     const gfp B = H + 2 * WIDE_HT * WIDE_HT * WIDE_FB;
-#ifdef MF_WIDE_NO_PREFETCH
-#pragma unroll
-    for (int rt = 0; rt < WIDE_HT; ++rt) {
-        if (rt < sp.ht) {
-            f32x16_t acc = wide_bias(B, rt, hh);
-#pragma unroll
-            for (int it = 0; it < WIDE_HT; ++it)
-                if (it < sp.nin_h[rt]) wide_block(acc, H + (rt * WIDE_HT + it) * WIDE_FB, lane, TileB{in[it]});
-            wide_relu(acc);
-            out[rt] = acc;
-        } else {
-            out[rt] = wide_zero();
-        }
-    }
-#else
     if constexpr (PAIR) {
         Frag2 cur, nxt;
         frag2_load(cur, H, lane);                                 // pair (0, 0): every tile in use has at least one input tile
@@ -295,7 +279,6 @@ __device__ __forceinline__ void wide_hidden(gfp H, const f32x16_t (&in)[WIDE_HT]
         }
     }
     }
-#endif
 }
 
 // v = (output block) h + b : NRT row tiles of the block (2: the 64 spline slots of both halves; 1: the affine block)
@@ -303,22 +286,6 @@ template <int NRT, bool PAIR>
 __device__ __forceinline__ void wide_out_block(gfp blk, const f32x16_t (&h)[WIDE_HT], float (&v)[32], int lane,
                                                int hh, int nin) {
     const gfp B = blk + 4 * WIDE_HT * WIDE_FB;
-#ifdef MF_WIDE_NO_PREFETCH
-#pragma unroll
-    for (int rt = 0; rt < 2; ++rt) {
-        if (rt < NRT) {
-            f32x16_t acc = wide_bias(B, rt, hh);
-#pragma unroll
-            for (int it = 0; it < WIDE_HT; ++it)
-                if (it < nin) wide_block(acc, blk + (rt * WIDE_HT + it) * WIDE_FB, lane, TileB{h[it]});
-#pragma unroll
-            for (int r = 0; r < 16; ++r) v[16 * rt + r] = acc[r];
-        } else {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) v[16 * rt + r] = 0.0f;
-        }
-    }
-#else
     if constexpr (PAIR) {
         Frag2 cur, nxt;
         if (nin > 0) frag2_load(cur, blk, lane);
@@ -365,7 +332,6 @@ __device__ __forceinline__ void wide_out_block(gfp blk, const f32x16_t (&h)[WIDE
         }
     }
     }
-#endif
 }
 
 // the affine transform's parameters of feature i out of the block's slots: slot i of half 0 = shift_i, of half 1 = scale_i
@@ -385,11 +351,7 @@ __device__ __forceinline__ void wide_store(float* __restrict__ dst, int rt, int 
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const float t = a[r];
-#ifdef MF_WIDE_PLAIN_STORES
-        base[r * 32] = t;
-#else
         MF_ACT_ST(base + r * 32, t);           // written once, read once by another kernel: non-temporal (26.6 vs 26.9 ms per step)
-#endif
     }
 }
 
@@ -520,11 +482,9 @@ __global__ __launch_bounds__(WIDE_BLOCK) MF_WAVES_PER_SIMD(2, 2) void wide_fwd_k
 }
 
 // =========================================================================================== backward
+// one wave per SIMD: ~400 registers (the level-L-1 tile, dL/dh, the spline's adjoint state)
 template <int K, bool SAVED>      // SAVED: the forward handed its activations over (act): nothing is recomputed
-#ifndef MF_WIDE_BWD_WAVES
-#define MF_WIDE_BWD_WAVES 1            // one wave per SIMD: ~400 registers (the level-L-1 tile, dL/dh, the spline's adjoint state)
-#endif
-__global__ __launch_bounds__(WIDE_BLOCK) MF_WAVES_PER_SIMD(MF_WIDE_BWD_WAVES, MF_WIDE_BWD_WAVES) void wide_bwd_kernel(
+__global__ __launch_bounds__(WIDE_BLOCK) MF_WAVES_PER_SIMD(1, 1) void wide_bwd_kernel(
     const float* __restrict__ image_arg, int d, int L, const float* __restrict__ x, int64_t n, const float* __restrict__ gy,
     const float* __restrict__ glogp, float* __restrict__ gx, float* __restrict__ scratch, WideSp sp, int bins_rt,
     const float* __restrict__ act) {
@@ -608,14 +568,6 @@ __global__ __launch_bounds__(WIDE_BLOCK) MF_WAVES_PER_SIMD(MF_WIDE_BWD_WAVES, MF
                 for (int m = 0; m < 32; ++m) gp[(32 * (m >> 4) + (m & 15)) * 32] = gv[m];
                 // gh += W3_i^T gphi  (contraction over the 64 padded rows of the block = the 32 slots of both halves)
                 const gfp T = blk + 2 * WIDE_HT * WIDE_FB;
-#ifdef MF_WIDE_NO_PREFETCH
-#pragma unroll
-                for (int it = 0; it < WIDE_HT; ++it)
-                    if (it < nin) {
-                        wide_block(gh[it], T + (it * 2 + 0) * WIDE_FB, lane, SlotB<0>{gv});
-                        wide_block(gh[it], T + (it * 2 + 1) * WIDE_FB, lane, SlotB<16>{gv});
-                    }
-#else
                 // (single blocks here: a pair in flight on top of the spline's adjoint state spills 50 registers — 15.6 vs 16.0 ms per
                 // step; requesting the NEXT output block's first fragments ahead of this chain measured nothing: 15.7 vs 15.6)
                 Frag cur, nxt;
@@ -630,7 +582,6 @@ __global__ __launch_bounds__(WIDE_BLOCK) MF_WAVES_PER_SIMD(MF_WIDE_BWD_WAVES, MF
                         frag_mfma(gh[it], cur, SlotB<16>{gv});
                         cur = nxt;
                     }
-#endif
             }
         } else {
             float v[32], gv[32];
@@ -673,17 +624,6 @@ __global__ __launch_bounds__(WIDE_BLOCK) MF_WAVES_PER_SIMD(MF_WIDE_BWD_WAVES, MF
                 }
                 const gfp T = image + g.offH + (l - 1) * g.strideH + WIDE_HT * WIDE_HT * WIDE_FB;
                 f32x16_t t[WIDE_HT];
-#ifdef MF_WIDE_NO_PREFETCH
-#pragma unroll
-                for (int it = 0; it < WIDE_HT; ++it) {
-                    t[it] = wide_zero();
-                    if (it < sp.ht) {
-#pragma unroll
-                        for (int kt = 0; kt < WIDE_HT; ++kt)
-                            if (kt >= sp.kbeg_t[it] && kt < sp.ht) wide_block(t[it], T + (it * WIDE_HT + kt) * WIDE_FB, lane, TileB{gh[kt]});
-                    }
-                }
-#else
                 Frag2 cur, nxt;
                 frag2_load(cur, T, lane);                         // pair (0, 0): kbeg_t[0] = 0
 #pragma unroll
@@ -702,7 +642,6 @@ __global__ __launch_bounds__(WIDE_BLOCK) MF_WAVES_PER_SIMD(MF_WIDE_BWD_WAVES, MF
                             }
                     }
                 }
-#endif
 #pragma unroll
                 for (int it = 0; it < WIDE_HT; ++it) gh[it] = t[it];
             }
@@ -749,17 +688,11 @@ struct WideJobs {
     WideJob job[WIDE_MAXJOBS];
 };
 constexpr int WIDE_OA_WAVES = 4;
-// B column tiles per job.  2: 64 x 64 blocks, 136 registers, three waves per SIMD.  -DMF_WIDE_OA_FAT: 64 x 128 blocks (each A pair read
-// once per layer: 0.76 of the bytes) at 216 registers, two waves per SIMD — measured slower (11.7 vs 10.4 ms per step at 128 units).
-#ifdef MF_WIDE_OA_FAT
-constexpr int WIDE_OA_NB = WIDE_HT;
-#define MF_WIDE_OA_OCC 2
-#else
+// B column tiles per job.  2: 64 x 64 blocks, 136 registers, three waves per SIMD.  64 x 128 blocks (each A pair read once per
+// layer: 0.76 of the bytes) at 216 registers, two waves per SIMD, measured slower (11.7 vs 10.4 ms per step at 128 units).
 constexpr int WIDE_OA_NB = 2;
-#define MF_WIDE_OA_OCC 3
-#endif
 
-__global__ __launch_bounds__(64 * WIDE_OA_WAVES) MF_WAVES_PER_SIMD(MF_WIDE_OA_OCC, MF_WIDE_OA_OCC) void wide_outer_accum_kernel(const float* __restrict__ scratch,
+__global__ __launch_bounds__(64 * WIDE_OA_WAVES) MF_WAVES_PER_SIMD(3, 3) void wide_outer_accum_kernel(const float* __restrict__ scratch,
                                                                               const float* __restrict__ actbuf,
                                                                               const float* __restrict__ x, int64_t n, int d,
                                                                               float* __restrict__ gslab, int64_t gtotal,

@@ -32,135 +32,160 @@ def kde_radius(bandwidth_in_bins: float) -> int:
 
 
 # ------------------------------------------------------------------------------------------------ flow
+# One class per kernel family (include/mentflow_hip.h): its entry points and size queries.  FlowSpec picks the family once;
+# the layer loops below call through it.  `shape` = the arguments between `image` and `order`; fwd / bwd return the entry point
+# of a hand-off level and the arguments that follow `init_logp` / `accumulate`.
+class _NarrowRqs:
+    """mf_flow_rqs_*: the 64-wide spline kernels (weights in LDS).  Fused backward where the layer's mask structure and LDS
+    budget allow (mf_flow_set_bwd_variant can force the two-kernel path); hand-off levels 1 and 2."""
+    inv = "mf_flow_rqs_layer_inv"
+    saved_whole = False     # the saved-activation backward is the fused kernel: no scratch, one chunk anyway
+
+    def __init__(self, s: "FlowSpec"):
+        self.s, self.shape = s, (s.d, s.L, s.bins)
+
+    def fwd(self, act, level):
+        return ("mf_flow_rqs_layer_fwd_save", (ptr(act), act.numel(), level)) if level > 0 else ("mf_flow_rqs_layer_fwd", ())
+
+    def bwd(self, scratch, act, level):
+        return (("mf_flow_rqs_layer_bwd_saved", (ptr(act), act.numel(), level)) if level > 0 else
+                ("mf_flow_rqs_layer_bwd", (ptr(scratch), scratch.numel())))
+
+    def scratch_floats(self, n):
+        return max(_lib.get_lib().mf_flow_bwd_scratch_floats(n, self.s.d, self.s.L, o) for o in self.s.orders)
+
+    def slab_rows(self, n):
+        r = {_lib.get_lib().mf_flow_bwd_slab_rows(n, self.s.d, self.s.L, o) for o in self.s.orders}
+        if len(r) != 1:
+            raise RuntimeError("layers of one flow disagree on the backward variant")
+        return r.pop()
+
+    def act_floats(self, n, level):
+        return _lib.get_lib().mf_flow_rqs_act_floats(n, self.s.d, self.s.L, self.s.bins, level)
+
+    def top_level(self):    # under the CURRENT backward variant (0 for the two-kernel path)
+        return min(_lib.get_lib().mf_flow_rqs_act_level(self.s.d, self.s.L, self.s.bins, o) for o in self.s.orders)
+
+
+class _NarrowAffine:
+    """mf_flow_affine_*: the 64-wide affine kernels (weights in LDS); no activation hand-off."""
+    inv = "mf_flow_affine_layer_inv"
+    saved_whole = False
+
+    def __init__(self, s: "FlowSpec"):
+        self.s, self.shape = s, (s.d, s.L)
+
+    def fwd(self, act, level):
+        return "mf_flow_affine_layer_fwd", ()
+
+    def bwd(self, scratch, act, level):
+        return "mf_flow_affine_layer_bwd", (ptr(scratch), scratch.numel())
+
+    def scratch_floats(self, n):
+        return _lib.get_lib().mf_flow_affine_bwd_scratch_floats(n, self.s.L)
+
+    def slab_rows(self, n):
+        return _lib.get_lib().mf_flow_affine_bwd_slab_rows(n)
+
+    def act_floats(self, n, level):
+        return 0
+
+    def top_level(self):
+        return 0
+
+
+class _Wide:
+    """mf_flow_wide_*: hidden_units 65 .. 128 and / or 8 .. 16 features.  Weights in global memory as MFMA fragments, two-kernel
+    backward, gradient slabs in natural order; one hand-off level (hidden tiles + conditioner outputs)."""
+    inv = "mf_flow_wide_layer_inv"
+    saved_whole = True      # the saved activations cover the batch as one tile sequence: one chunk whatever the scratch costs
+
+    def __init__(self, s: "FlowSpec"):
+        self.s, self.bins = s, (s.bins if s.kind == "rqs" else 0)
+        self.shape = (s.d, s.hidden, s.L, self.bins)
+
+    def fwd(self, act, level):
+        return ("mf_flow_wide_layer_fwd_save", (ptr(act), act.numel())) if level > 0 else ("mf_flow_wide_layer_fwd", ())
+
+    def bwd(self, scratch, act, level):
+        tail = (ptr(scratch), scratch.numel())
+        return ("mf_flow_wide_layer_bwd_saved", tail + (ptr(act), act.numel())) if level > 0 else ("mf_flow_wide_layer_bwd", tail)
+
+    def scratch_floats(self, n):
+        return _lib.get_lib().mf_flow_wide_bwd_scratch_floats(n, self.s.d, self.s.L, self.bins)
+
+    def slab_rows(self, n):
+        return _lib.get_lib().mf_flow_wide_bwd_slab_rows(n)
+
+    def act_floats(self, n, level):
+        return _lib.get_lib().mf_flow_wide_act_floats(n, self.s.d, self.s.L, self.bins)
+
+    def top_level(self):
+        return 1
+
+
 class FlowSpec:
-    """Static description of a packed flow (shared by every call): geometry + device index maps."""
+    """Static description of a packed flow (shared by every call): geometry, kernel family + device index maps."""
 
     def __init__(self, d: int, hidden_layers: int, transforms: int, kind: str, bins: int, image_floats: int,
                  image_index: torch.Tensor, grad_index: torch.Tensor, orders, wide: bool = False, hidden: int = 64,
                  grad_floats: Optional[int] = None):
-        self.d, self.L, self.T, self.kind, self.bins = d, hidden_layers, transforms, kind, bins
-        # wide = the mf_flow_wide_* family (hidden_units 65 .. 128 and / or 8 .. 16 features: weights in global memory as MFMA
-        # fragments, two-kernel backward, gradient slabs of `grad_floats` floats in natural order)
-        self.wide, self.hidden = bool(wide), int(hidden)
+        self.d, self.L, self.T, self.kind, self.bins, self.hidden = d, hidden_layers, transforms, kind, bins, int(hidden)
         self.grad_floats = int(image_floats if grad_floats is None else grad_floats)
         # per layer: host int32 array of the autoregressive order (lets the kernels skip masked-out MFMA k-steps)
         self.orders = [(C.c_int32 * d)(*[int(v) for v in o]) for o in orders]
-        self.sparse = True
+        self.family = _Wide(self) if wide else (_NarrowRqs(self) if kind == "rqs" else _NarrowAffine(self))
         self.image_floats = image_floats
         self.image_index = image_index      # int32 [T * image_floats]  -> flat parameter index or -1
         self.grad_index = grad_index        # int32 [numel]             -> position in the image stack or -1
         self.bwd_chunk = 1 << 20            # particles per backward chunk (3 KiB of scratch each at d=6)
-        # Activation hand-off from the training forward to the fused backward through HBM (mf_flow_rqs_layer_fwd_save):
-        # None = the highest level (2: hidden tiles + conditioner outputs, 1: hidden tiles, 0: recompute everything) that the
-        # kernels support for this flow AND whose buffers (T layers x 1 712 / 512 B per particle at d = 6, L = 3, 20 bins) fit
+        # Activation hand-off from the training forward to the backward through HBM (mf_flow_rqs_layer_fwd_save): None = the
+        # highest level (2: hidden tiles + conditioner outputs, 1: hidden tiles, 0: recompute everything) that the family's
+        # kernels take for this flow AND whose buffers (T layers x 1 712 / 512 B per particle at d = 6, L = 3, 20 bins) fit
         # `act_budget_bytes`; an int pins the level (tests, A/B runs).  Environment: MENTFLOW_ACT_LEVEL.
         self.act_level: Optional[int] = _ENV_ACT_LEVEL
         self.act_budget_bytes: Optional[int] = None     # None: 60 % of the device's memory (173 GB on an MI355X)
-        self._act_supported: Optional[int] = None
 
     def resolve_act_level(self, n: int, device: torch.device) -> int:
+        """The wanted level (act_level, capped by the family's highest), stepped down while T layers of buffers exceed the
+        budget."""
         if n <= 0:
             return 0
-        lib = _lib.get_lib()
-        if self.wide:
-            # one level: hidden tiles + conditioner outputs (mf_flow_wide_layer_fwd_save), if T such buffers fit the budget
-            want = 1 if self.act_level is None else min(int(self.act_level), 1)
-            budget = self.act_budget_bytes
-            if budget is None:
-                budget = int(0.6 * torch.cuda.get_device_properties(device).total_memory) if device.type == "cuda" else 1 << 62
-            bins = self.bins if self.kind == "rqs" else 0
-            return want if want > 0 and 4 * self.T * lib.mf_flow_wide_act_floats(n, self.d, self.L, bins) <= budget else 0
-        if self.kind != "rqs" or not self.sparse:
+        top = self.family.top_level()
+        level = top if self.act_level is None else min(int(self.act_level), top)
+        if level <= 0:
             return 0
-        supported = min(lib.mf_flow_rqs_act_level(self.d, self.L, self.bins, o) for o in self.orders)
-        want = supported if self.act_level is None else min(int(self.act_level), supported)
         budget = self.act_budget_bytes
         if budget is None:
             budget = int(0.6 * torch.cuda.get_device_properties(device).total_memory) if device.type == "cuda" else 1 << 62
-        while want > 0 and 4 * self.T * lib.mf_flow_rqs_act_floats(n, self.d, self.L, self.bins, want) > budget:
-            want -= 1
-        return want
+        while level > 0 and 4 * self.T * self.family.act_floats(n, level) > budget:
+            level -= 1
+        return level
 
 
 def _layer_fwd(spec: FlowSpec, t: int, image: torch.Tensor, x: torch.Tensor, y: torch.Tensor,
                logp_in: Optional[torch.Tensor], logp_out: torch.Tensor, init: bool, act: Optional[torch.Tensor] = None,
                act_level: int = 0) -> None:
-    n = x.shape[0]
-    order = spec.orders[t] if spec.sparse else None
-    if spec.wide and act_level > 0:
-        call("mf_flow_wide_layer_fwd_save", ptr(image), spec.d, spec.hidden, spec.L, spec.bins if spec.kind == "rqs" else 0, order,
-             ptr(x), n, ptr(y), ptr(logp_in), ptr(logp_out), int(init), ptr(act), act.numel(), stream_ptr(x))
-    elif spec.wide:
-        call("mf_flow_wide_layer_fwd", ptr(image), spec.d, spec.hidden, spec.L, spec.bins if spec.kind == "rqs" else 0, order,
-             ptr(x), n, ptr(y), ptr(logp_in), ptr(logp_out), int(init), stream_ptr(x))
-    elif act_level > 0:
-        call("mf_flow_rqs_layer_fwd_save", ptr(image), spec.d, spec.L, spec.bins, order, ptr(x), n, ptr(y), ptr(logp_in),
-             ptr(logp_out), int(init), ptr(act), act.numel(), int(act_level), stream_ptr(x))
-    elif spec.kind == "rqs":
-        call("mf_flow_rqs_layer_fwd", ptr(image), spec.d, spec.L, spec.bins, order, ptr(x), n, ptr(y), ptr(logp_in),
-             ptr(logp_out), int(init), stream_ptr(x))
-    else:
-        call("mf_flow_affine_layer_fwd", ptr(image), spec.d, spec.L, order, ptr(x), n, ptr(y), ptr(logp_in),
-             ptr(logp_out), int(init), stream_ptr(x))
+    name, tail = spec.family.fwd(act, act_level)
+    call(name, ptr(image), *spec.family.shape, spec.orders[t], ptr(x), x.shape[0], ptr(y), ptr(logp_in), ptr(logp_out),
+         int(init), *tail, stream_ptr(x))
 
 
 def _layer_bwd(spec: FlowSpec, t: int, image, x, gy, glogp, gx, gslab, accumulate: bool, scratch, act=None,
                act_level: int = 0) -> None:
-    n = x.shape[0]
-    order = spec.orders[t] if spec.sparse else None
-    rows = gslab.shape[0]
-    if spec.wide and act_level > 0:
-        call("mf_flow_wide_layer_bwd_saved", ptr(image), spec.d, spec.hidden, spec.L, spec.bins if spec.kind == "rqs" else 0, order,
-             ptr(x), n, ptr(gy), ptr(glogp), ptr(gx), ptr(gslab), rows, int(accumulate), ptr(scratch), scratch.numel(), ptr(act),
-             act.numel(), stream_ptr(x))
-    elif spec.wide:
-        call("mf_flow_wide_layer_bwd", ptr(image), spec.d, spec.hidden, spec.L, spec.bins if spec.kind == "rqs" else 0, order,
-             ptr(x), n, ptr(gy), ptr(glogp), ptr(gx), ptr(gslab), rows, int(accumulate), ptr(scratch), scratch.numel(),
-             stream_ptr(x))
-    elif act_level > 0:
-        call("mf_flow_rqs_layer_bwd_saved", ptr(image), spec.d, spec.L, spec.bins, order, ptr(x), n, ptr(gy), ptr(glogp),
-             ptr(gx), ptr(gslab), rows, int(accumulate), ptr(act), act.numel(), int(act_level), stream_ptr(x))
-    elif spec.kind == "rqs":
-        call("mf_flow_rqs_layer_bwd", ptr(image), spec.d, spec.L, spec.bins, order, ptr(x), n, ptr(gy), ptr(glogp),
-             ptr(gx), ptr(gslab), rows, int(accumulate), ptr(scratch), scratch.numel(), stream_ptr(x))
-    else:
-        call("mf_flow_affine_layer_bwd", ptr(image), spec.d, spec.L, order, ptr(x), n, ptr(gy), ptr(glogp), ptr(gx),
-             ptr(gslab), rows, int(accumulate), ptr(scratch), scratch.numel(), stream_ptr(x))
+    name, tail = spec.family.bwd(scratch, act, act_level)
+    call(name, ptr(image), *spec.family.shape, spec.orders[t], ptr(x), x.shape[0], ptr(gy), ptr(glogp), ptr(gx), ptr(gslab),
+         gslab.shape[0], int(accumulate), *tail, stream_ptr(x))
 
 
-def _bwd_plan(spec: FlowSpec, n: int, whole: bool = False):
-    """(chunk, scratch_floats, slab_rows) of a backward pass over n particles: the fused kernels need no scratch and
-    take the whole batch in one launch per layer; the two-kernel path is chunked to bound its hand-off scratch.  Every
-    chunk of a pass must write the same number of slab rows (each workgroup accumulates into its own row), so a ragged
-    last chunk is only allowed when it does."""
-    lib = _lib.get_lib()
-    if spec.wide:
-        def need(m):
-            return lib.mf_flow_wide_bwd_scratch_floats(m, spec.d, spec.L, spec.bins if spec.kind == "rqs" else 0)
-
-        def rows(m):
-            return lib.mf_flow_wide_bwd_slab_rows(m)
-    elif spec.kind == "rqs":
-        orders = spec.orders if spec.sparse else [None]
-
-        def need(m):
-            return max(lib.mf_flow_bwd_scratch_floats(m, spec.d, spec.L, o) for o in orders)
-
-        def rows(m):
-            r = {lib.mf_flow_bwd_slab_rows(m, spec.d, spec.L, o) for o in orders}
-            if len(r) != 1:
-                raise RuntimeError("layers of one flow disagree on the backward variant")
-            return r.pop()
-    else:
-        def need(m):
-            return lib.mf_flow_affine_bwd_scratch_floats(m, spec.L)
-
-        def rows(m):
-            return lib.mf_flow_affine_bwd_slab_rows(m)
-
-    # whole: one chunk whatever the scratch costs (the wide family's saved activations cover the batch as one tile sequence)
-    chunk = n if (need(n) == 0 or whole) else min(n, spec.bwd_chunk)
-    return chunk, need(chunk), rows
+def _bwd_plan(spec: FlowSpec, n: int, level: int):
+    """(chunk, scratch_floats) of a backward pass over n particles: the fused kernels need no scratch and take the whole
+    batch in one launch per layer; the two-kernel path is chunked to bound its hand-off scratch.  Every chunk of a pass must
+    write the same number of slab rows (each workgroup accumulates into its own row), so a ragged last chunk is only allowed
+    when it does."""
+    fam = spec.family
+    chunk = n if (fam.scratch_floats(n) == 0 or (level > 0 and fam.saved_whole)) else min(n, spec.bwd_chunk)
+    return chunk, fam.scratch_floats(chunk)
 
 
 def pack_images(spec: FlowSpec, flat: torch.Tensor) -> torch.Tensor:
@@ -193,12 +218,7 @@ class FlowSampleFn(torch.autograd.Function):
         images = pack_images(spec, flat)
         logp = torch.empty(n, dtype=_F32, device=z.device)
         level = spec.resolve_act_level(n, z.device)
-        act = None
-        if level > 0 and spec.wide:
-            act = torch.empty(spec.T, _lib.get_lib().mf_flow_wide_act_floats(n, spec.d, spec.L, spec.bins if spec.kind == "rqs" else 0),
-                              dtype=_F32, device=z.device)
-        elif level > 0:
-            act = torch.empty(spec.T, _lib.get_lib().mf_flow_rqs_act_floats(n, spec.d, spec.L, spec.bins, level), dtype=_F32, device=z.device)
+        act = torch.empty(spec.T, spec.family.act_floats(n, level), dtype=_F32, device=z.device) if level > 0 else None
         xs = [z]
         for t in range(spec.T):
             y = torch.empty_like(z)
@@ -222,7 +242,7 @@ class FlowSampleFn(torch.autograd.Function):
         gx = torch.zeros(n, spec.d, dtype=_F32, device=dev) if gx is None else _f32c(gx)
         glogp = torch.zeros(n, dtype=_F32, device=dev) if glogp is None else _f32c(glogp)
         level = ctx.act_level
-        chunk, scratch_floats, rows_of = _bwd_plan(spec, n, whole=spec.wide and level > 0)
+        chunk, scratch_floats = _bwd_plan(spec, n, level)
         act = act if level > 0 else None
         if level > 0 and chunk != n:
             raise RuntimeError("the backward variant changed between forward and backward: the saved activations belong to the "
@@ -232,7 +252,7 @@ class FlowSampleFn(torch.autograd.Function):
         spans = [(a, min(n, a + chunk)) for a in range(0, n, chunk)]
         groups = {}
         for a, b in spans:
-            groups.setdefault(rows_of(b - a), []).append((a, b))
+            groups.setdefault(spec.family.slab_rows(b - a), []).append((a, b))
         gflat = None
         g = gx
         slabs = {r: torch.empty(spec.T, r, spec.grad_floats, dtype=_F32, device=dev) for r in groups}
@@ -280,15 +300,8 @@ def flow_layers_inverse(x: torch.Tensor, flat: torch.Tensor, spec: FlowSpec) -> 
     zs = [x]
     for t in reversed(range(spec.T)):
         out = torch.empty_like(x)
-        if spec.wide:
-            call("mf_flow_wide_layer_inv", ptr(images[t]), spec.d, spec.hidden, spec.L, spec.bins if spec.kind == "rqs" else 0,
-                 spec.orders[t], ptr(zs[-1]), x.shape[0], ptr(out), stream_ptr(x))
-        elif spec.kind == "rqs":
-            call("mf_flow_rqs_layer_inv", ptr(images[t]), spec.d, spec.L, spec.bins, spec.orders[t], ptr(zs[-1]),
-                 x.shape[0], ptr(out), stream_ptr(x))
-        else:
-            call("mf_flow_affine_layer_inv", ptr(images[t]), spec.d, spec.L, spec.orders[t], ptr(zs[-1]), x.shape[0],
-                 ptr(out), stream_ptr(x))
+        call(spec.family.inv, ptr(images[t]), *spec.family.shape, spec.orders[t], ptr(zs[-1]), x.shape[0], ptr(out),
+             stream_ptr(x))
         zs.append(out)
     return zs
 
