@@ -255,6 +255,51 @@ int mf_mc_entropy_sums(const float* x, const float* logp, int64_t n, int d, floa
 int mf_scale_rows(const float* x, int64_t n, int d, const float* coef, float cscale, float* gx, int accumulate,
                   void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Classical MENT  (mentflow/ment.py:20-52,225-318; mentflow/sample.py:26-113).  Added at ABI version 5: the entry points
+ * below are purely additive (no existing signature or behaviour changed), so MF_ABI_VERSION stays 5.
+ *
+ * Slots: `nslot` (transform, diagnostic) pairs, each a DEVICE float descriptor of 24 floats
+ *   [0:8) row r0, [8:16) row r1 (2-D slots; zero-padded beyond d), [16] c0_x, [17] c_last_x, [18] 1/delta_x,
+ *   [19] c0_y, [20] c_last_y, [21] 1/delta_y, [22:24) unused
+ * and a DEVICE int32 meta row of 4: [ndim (1|2), Bx, By, offset of the slot's table in `tables`].  Tables are the
+ * Lagrange-function values at the bin centres, [Bx] or [Bx, By] row-major, concatenated (fp32).
+ *   h_s(x) = linear / bilinear interpolation of the table at u = (r0.x[, r1.x]); 0 outside [c0, c_last] on either axis;
+ *            NaN for a NaN coordinate; clamped to [0, 1e10].
+ *   prob(x) = prod_s h_s(x) * prior(x);  prior_kind 0: 1, 1: exp(prior_lognorm - |x|^2 / (2 prior_a^2)) (prior.Gaussian),
+ *            2: exp(prior_lognorm) on [-prior_a, prior_a]^d, else 0.
+ * 1 <= d <= 8, 0 <= nslot <= 512.  Sums are fp64 in a fixed order, no float atomics: outputs are bitwise reproducible.
+ *
+ * mf_ment_prob:       out[p] = prob(x[p])   (multiply != 0: out[p] *= prob(x[p]), for chains of pre-transforms).
+ * mf_ment_prob_grid:  the same on the implicit tensor grid of ncells = prod(shape) < 2^31 cells, cell q (ij order, last
+ *                     axis fastest) at (coords_0[i_0], ..., coords_{d-1}[i_{d-1}]) (`coords` concatenated per axis;
+ *                     `shape` is a HOST array of d), prob[q] written, and block_sums[b] = fp64 sum of (prob[q] + 1e-15f)
+ *                     over the cells of block b (mf_ment_blocks(ncells) blocks of 1024 consecutive cells).
+ * mf_ment_block_sums: those block sums for a given buffer prob[ncells].
+ * mf_ment_sample:     inverse-CDF draws from the cells of prob[shape] with weights prob + 1e-15 (sample_hist_bins):
+ *                     rnd[size, 1 + 2d] uniforms in [0, 1) (column 0 picks the cell, 1..d place the point uniformly in it,
+ *                     d+1..2d add 0.5 U(-delta, delta) per axis when noise != 0); `edges` = per-axis edge arrays (shape_j + 1
+ *                     each) concatenated; prefix = mf_ment_blocks(ncells) + 1 doubles of scratch; x[size, d] written.
+ * mf_ment_integrate:  pred[b] = sum_t prob(Minv u_bt) of one slot's line / plane integral: `coords` = per-axis u
+ *                     coordinates concatenated (counts[d] HOST), the nmeas measured axes meas_axes (HOST) index the bins in
+ *                     ij order in the order given, the other axes (ascending, ij order) the integration points t; minv is a
+ *                     HOST [d, d] array.  partial = mf_ment_integrate_ws_doubles(nbins, npoints) doubles of scratch.      */
+int64_t mf_ment_blocks(int64_t ncells);
+int64_t mf_ment_integrate_ws_doubles(int64_t nbins, int64_t npoints);
+int mf_ment_prob(const float* x, int64_t n, int d, int nslot, const float* desc, const int32_t* meta, const float* tables,
+                 int64_t table_floats, int prior_kind, float prior_a, float prior_lognorm, int multiply, float* out,
+                 void* stream);
+int mf_ment_prob_grid(const float* coords, const int64_t* shape, int d, int nslot, const float* desc, const int32_t* meta,
+                      const float* tables, int64_t table_floats, int prior_kind, float prior_a, float prior_lognorm,
+                      float* prob, double* block_sums, void* stream);
+int mf_ment_block_sums(const float* prob, int64_t ncells, double* block_sums, void* stream);
+int mf_ment_sample(const float* prob, const int64_t* shape, int d, const double* block_sums, double* prefix,
+                   const float* edges, const float* rnd, int64_t size, int noise, float* x, void* stream);
+int mf_ment_integrate(int d, const float* minv, const float* coords, const int64_t* counts, int nmeas,
+                      const int32_t* meas_axes, int nslot, const float* desc, const int32_t* meta, const float* tables,
+                      int64_t table_floats, int prior_kind, float prior_a, float prior_lognorm, double* partial,
+                      float* pred, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -82,6 +82,14 @@ PROTOTYPES = {
                                             _ptr, _ptr]),
     "mf_mc_entropy_sums": (_i32, [_ptr, _ptr, _i64, _i32, _ptr, _ptr, _ptr]),
     "mf_scale_rows": (_i32, [_ptr, _i64, _i32, _ptr, _f32, _ptr, _i32, _ptr]),
+    "mf_ment_blocks": (_i64, [_i64]),
+    "mf_ment_integrate_ws_doubles": (_i64, [_i64, _i64]),
+    "mf_ment_prob": (_i32, [_ptr, _i64, _i32, _i32, _ptr, _ptr, _ptr, _i64, _i32, _f32, _f32, _i32, _ptr, _ptr]),
+    "mf_ment_prob_grid": (_i32, [_ptr, _ptr, _i32, _i32, _ptr, _ptr, _ptr, _i64, _i32, _f32, _f32, _ptr, _ptr, _ptr]),
+    "mf_ment_block_sums": (_i32, [_ptr, _i64, _ptr, _ptr]),
+    "mf_ment_sample": (_i32, [_ptr, _ptr, _i32, _ptr, _ptr, _ptr, _ptr, _i64, _i32, _ptr, _ptr]),
+    "mf_ment_integrate": (_i32, [_i32, _ptr, _ptr, _ptr, _i32, _ptr, _i32, _ptr, _ptr, _ptr, _i64, _i32, _f32, _f32, _ptr,
+                                 _ptr, _ptr]),
 }
 
 

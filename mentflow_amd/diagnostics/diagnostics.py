@@ -170,6 +170,12 @@ class Histogram1D(Histogram):
         self.uniform = is_uniform_axis(edges)
         self.cell_value = self.resolution_value if self.uniform else float(self.coords[1] - self.coords[0])
 
+    def project(self, x: torch.Tensor) -> torch.Tensor:
+        """diagnostics.py:116-122: x[:, axis], or x . direction."""
+        if self.direction is None:
+            return x[:, self.axis]
+        return torch.sum(x * self.direction.to(x), dim=1)
+
     def projection_rows(self, matrix: torch.Tensor) -> List[torch.Tensor]:
         """u[:, axis] = x . matrix[axis]  (or  (x @ M.T) . direction = x . (direction @ M))."""
         if self.direction is None:
@@ -225,6 +231,15 @@ class Histogram2D(Histogram):
     @property
     def edges(self) -> Tuple[torch.Tensor, torch.Tensor]:
         return (self.edges_x, self.edges_y)
+
+    @property
+    def shape(self) -> Tuple[int, int]:
+        """(Bx, By): the shape of one projection (used by MENT's integrate mode)."""
+        return (self.coords_x.numel(), self.coords_y.numel())
+
+    def project(self, x: torch.Tensor) -> torch.Tensor:
+        """diagnostics.py:179-180."""
+        return x[:, self.axis]
 
     def projection_rows(self, matrix: torch.Tensor) -> List[torch.Tensor]:
         return [matrix[self.axis[0]], matrix[self.axis[1]]]

@@ -461,3 +461,87 @@ def proj_hist_counts_2d(x, V0, V1, edges_x, edges_y) -> torch.Tensor:
     call("mf_proj_hist2d_counts", ptr(x), x.shape[0], x.shape[1], ptr(V0), ptr(V1), P, ptr(ex), Bx, ptr(ey), By,
          ptr(counts), stream_ptr(x))
     return counts
+
+
+# ------------------------------------------------------------------------------------------------ classical MENT
+# Thin wrappers over mf_ment_* (include/mentflow_hip.h); mentflow_amd/ment.py builds the slot descriptors.  `prior` is the
+# (kind, a, lognorm) triple of the header: kind 0 none, 1 Gaussian, 2 uniform box.
+MENT_DESC = 24
+
+
+def _host_i64(values):
+    arr = (C.c_int64 * len(values))(*[int(v) for v in values])
+    return arr, C.cast(arr, C.c_void_p)
+
+
+def ment_prob(x: torch.Tensor, desc: torch.Tensor, meta: torch.Tensor, tables: torch.Tensor, prior=(0, 0.0, 0.0),
+              out: Optional[torch.Tensor] = None, multiply: bool = False) -> torch.Tensor:
+    """prod over slots of the interpolated Lagrange functions at x[n, d], times the prior; multiply=True: out *= that."""
+    x, tables = _f32c(x), _f32c(tables)
+    if out is None:
+        out = torch.empty(x.shape[0], dtype=_F32, device=x.device)
+    call("mf_ment_prob", ptr(x), x.shape[0], x.shape[1], desc.shape[0], ptr(desc), ptr(meta), ptr(tables), tables.numel(),
+         int(prior[0]), float(prior[1]), float(prior[2]), int(bool(multiply)), ptr(out), stream_ptr(x))
+    return out
+
+
+def ment_prob_grid(coords: List[torch.Tensor], desc, meta, tables, prior=(0, 0.0, 0.0)) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(prob[prod(shape)], fp64 block sums of prob + 1e-15) on the implicit grid of the given per-axis cell centres."""
+    tables = _f32c(tables)
+    cat = _f32c(torch.cat([c.reshape(-1) for c in coords]))
+    shape = [c.numel() for c in coords]
+    n = math.prod(shape)
+    prob = torch.empty(n, dtype=_F32, device=cat.device)
+    sums = torch.empty(max(1, int(_lib.get_lib().mf_ment_blocks(n))), dtype=torch.float64, device=cat.device)
+    keep, shp = _host_i64(shape)
+    call("mf_ment_prob_grid", ptr(cat), shp, len(shape), desc.shape[0], ptr(desc), ptr(meta), ptr(tables), tables.numel(),
+         int(prior[0]), float(prior[1]), float(prior[2]), ptr(prob), ptr(sums), stream_ptr(cat))
+    return prob, sums
+
+
+def ment_block_sums(prob: torch.Tensor) -> torch.Tensor:
+    prob = _f32c(prob.reshape(-1))
+    sums = torch.empty(max(1, int(_lib.get_lib().mf_ment_blocks(prob.numel()))), dtype=torch.float64, device=prob.device)
+    call("mf_ment_block_sums", ptr(prob), prob.numel(), ptr(sums), stream_ptr(prob))
+    return sums
+
+
+def ment_sample(prob: torch.Tensor, shape, block_sums: torch.Tensor, edges: List[torch.Tensor], size: int, noise: bool,
+                rnd: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x[size, len(shape)]: cells drawn with probability (prob + 1e-15) / sum, points uniform in the cell (+ the
+    0.5 U(-delta, delta) noise per axis).  rnd: [size, 1 + 2 d] uniforms (default torch.rand on the device)."""
+    prob = _f32c(prob.reshape(-1))
+    d = len(shape)
+    if rnd is None:
+        rnd = torch.rand(int(size), 1 + 2 * d, device=prob.device)
+    rnd = _f32c(rnd)
+    cat = _f32c(torch.cat([e.reshape(-1).to(prob.device, _F32) for e in edges]))
+    prefix = torch.empty(block_sums.numel() + 1, dtype=torch.float64, device=prob.device)
+    x = torch.empty(int(size), d, dtype=_F32, device=prob.device)
+    keep, shp = _host_i64(shape)
+    call("mf_ment_sample", ptr(prob), shp, d, ptr(block_sums), ptr(prefix), ptr(cat), ptr(rnd), int(size), int(bool(noise)),
+         ptr(x), stream_ptr(prob))
+    return x
+
+
+def ment_integrate(minv: torch.Tensor, coords: List[torch.Tensor], meas_axes, desc, meta, tables,
+                   prior=(0, 0.0, 0.0)) -> torch.Tensor:
+    """pred[b] = sum_t prob(Minv u_bt) (fp64 sums, fixed order): coords[a] = the u coordinates of axis a (bin centres on the
+    measured axes, the integration grid on the others).  Returns the flat [nbins] projection (ij order of meas_axes)."""
+    tables = _f32c(tables)
+    d = len(coords)
+    cat = _f32c(torch.cat([c.reshape(-1) for c in coords]))
+    counts = [c.numel() for c in coords]
+    nbins = math.prod(counts[a] for a in meas_axes)
+    npoints = math.prod(counts) // nbins
+    m = minv.detach().to("cpu", torch.float32).contiguous().reshape(-1).tolist()
+    mh = (C.c_float * (d * d))(*m)
+    keep, cnt = _host_i64(counts)
+    ma = (C.c_int32 * len(meas_axes))(*[int(a) for a in meas_axes])
+    partial = torch.empty(max(1, int(_lib.get_lib().mf_ment_integrate_ws_doubles(nbins, npoints))), dtype=torch.float64,
+                          device=cat.device)
+    pred = torch.empty(nbins, dtype=_F32, device=cat.device)
+    call("mf_ment_integrate", d, C.cast(mh, C.c_void_p), ptr(cat), cnt, len(meas_axes), C.cast(ma, C.c_void_p),
+         desc.shape[0], ptr(desc), ptr(meta), ptr(tables), tables.numel(), int(prior[0]), float(prior[1]), float(prior[2]),
+         ptr(partial), ptr(pred), stream_ptr(cat))
+    return pred

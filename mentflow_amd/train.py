@@ -168,3 +168,38 @@ class Trainer:
             final_epoch = converged
             D_norm_old = D_norm
         model.load_state_dict(best_state_dict)
+
+
+class MENTTrainer(Trainer):
+    """Trainer for the classical MENT solver (mentflow/train/train.py:286-349): epoch 0 only evaluates, every later epoch
+    is one ``model.gauss_seidel_update(lr, thresh)``.  ``self.history`` gets epoch, iteration, time and D_norm per epoch;
+    D_norm is the ``discrepancy`` of the dict the eval callable returns (None without one: the reference logs None), and
+    training stops once that discrepancy is <= dmax."""
+
+    def __init__(self, model=None, plot: Optional[Callable] = None, eval: Optional[Callable] = None,
+                 output_dir: Optional[str] = None, notebook: bool = False) -> None:
+        super().__init__(model=model, optimizer=None, lr_scheduler=None, plot=plot, eval=eval, output_dir=output_dir,
+                         notebook=notebook)
+
+    def train(self, epochs: int, lr: float = 0.99, thresh: float = 1.00e-10, savefig_kws: Optional[dict] = None,
+              dmax: float = 0.0) -> None:
+        if not savefig_kws:
+            savefig_kws = dict()
+        savefig_kws.setdefault("dpi", 300)
+        iteration = 0
+        start_time = time.time()
+        for epoch in range(epochs + 1):
+            if epoch > 0:
+                if self.verbose:
+                    print("epoch = {}".format(epoch))
+                self.model.gauss_seidel_update(lr=lr, thresh=thresh)
+            result = self.eval(self.model) if self.eval is not None else None
+            if self.plot is not None:
+                self.plot(self.model)
+            discrepancy = result.get("discrepancy") if isinstance(result, dict) else None
+            self._log(dict(epoch=epoch, iteration=iteration, time=time.time() - start_time,
+                           D_norm=None if discrepancy is None else float(discrepancy)))
+            if discrepancy is not None and discrepancy <= dmax:
+                if self.verbose:
+                    print("CONVERGED (dmax)")
+                return
