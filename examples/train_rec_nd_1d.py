@@ -2,7 +2,9 @@
 """End-to-end MENT-Flow reconstruction on one MI355X — the hydra-free equivalent of
 `experiments/rec_nd_1d/train_flow.py ndim=6 seed=2 meas.num=25 meas.bins=64 meas.xmax=4.0 dist.name=rings +dist.decay=0.2
 model.prior_scale=1.0 gen.transforms=5 train.batch_size=25000` (experiments/rec_nd_1d/run_rings.sh:33-44), with the
-penalty schedule of experiments/config/rec_nd_1d_flow.yaml (penalty 0 -> *1.5 + 50 per epoch, dmax 1e-4).
+penalty schedule of experiments/config/rec_nd_1d_flow.yaml (penalty 0 -> *1.5 + 50 per epoch, dmax 1e-4).  The eval hook is
+an mf.Evaluator (experiments/rec_nd_1d/setup.py::setup_eval): at the end of every epoch it prints the mean KL discrepancy of
+50 000 model samples and their sliced Wasserstein distance to 50 000 fresh ground-truth samples.
 
     python examples/train_rec_nd_1d.py --epochs 3 --iters 100 --batch-size 25000
 """
@@ -15,6 +17,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import mentflow_amd as mf                                    # noqa: E402
+from mentflow_amd.distributions import get_distribution      # noqa: E402
 from mentflow_amd.harness import build_problem               # noqa: E402
 
 
@@ -30,6 +33,7 @@ def main():
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--batch-size", type=int, default=25000)
     ap.add_argument("--lr", type=float, default=1e-3)
+    ap.add_argument("--eval-size", type=int, default=50000)
     ap.add_argument("--hidden-units", type=int, default=64, help="config/gen/flow.yaml:3; above 64 the wide kernel family runs")
     ap.add_argument("--hidden-layers", type=int, default=3)
     ap.add_argument("--graphed", action="store_true",
@@ -47,7 +51,10 @@ def main():
     opt = torch.optim.AdamW(model.parameters(), lr=args.lr, weight_decay=0.0,
                             **(dict(capturable=True, fused=True) if args.graphed else {}))
     sched = torch.optim.lr_scheduler.ReduceLROnPlateau(opt, min_lr=args.lr, patience=400, factor=0.1)
-    trainer = mf.train.Trainer(model, opt, sched, verbose=True, graphed=args.graphed)
+    dist_kws = dict(decay=0.2) if args.dist == "rings" else {}                 # the ground truth of build_problem
+    evaluate = mf.Evaluator(args.eval_size, distance=mf.loss.SlicedWassersteinDistance(n_projections=50, p=2, device=dev),
+                            distribution=get_distribution(args.dist, ndim=args.ndim, seed=args.seed, **dist_kws))
+    trainer = mf.train.Trainer(model, opt, sched, eval=evaluate, verbose=True, graphed=args.graphed)
     t0 = time.time()
     trainer.train(epochs=args.epochs, iterations=args.iters, batch_size=args.batch_size, rtol=-1, atol=-1, dmax=1e-4,
                   penalty_start=0.0, penalty_step=50.0, penalty_scale=1.5, eval_batch_size=100000)

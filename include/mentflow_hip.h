@@ -300,6 +300,33 @@ int mf_ment_integrate(int d, const float* minv, const float* coords, const int64
                       int64_t table_floats, int prior_kind, float prior_a, float prior_lognorm, double* partial,
                       float* pred, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Sliced Wasserstein distance  (mentflow/loss.py:20-42, where the 1-D transport cost is POT's ot.lp.wasserstein_1d on the
+ * host).  Purely additive entry points: MF_ABI_VERSION stays 5.  No float atomics, fp64 sums in a fixed order: every output
+ * is bitwise reproducible.  All sizes obey P * n < 2^31.
+ *
+ * mf_swd_project:        u[p, i] = sum_k x[i, k] * dir[k, p] for x[n, d] (1 <= d <= 8) and dir[d, P]; u is projection-major
+ *                        [P, n] so that each projection is one contiguous segment.
+ * mf_segsort_f32:        out[s, :] = keys[s, :] in ascending order for each of the P segments of n fp32 keys (keys only, no
+ *                        payload).  Order of torch.sort: NaN last (written back as a quiet NaN), -0.0 and +0.0 compare equal.
+ *                        Tiles of 2^tile_log2 keys are sorted in LDS, then merged pairwise in ceil(log2(tiles)) passes between
+ *                        `out` and the workspace; tile_log2 = 0 selects the built-in tile (2^12), 4..12 are accepted.
+ *                        `ws` = mf_segsort_workspace_bytes(P, n, tile_log2) bytes of device scratch (0: none needed, ws may be
+ *                        NULL; -1: bad arguments).  `out` may be `keys`.
+ * mf_swd_quantile_cost:  u[P, n1], v[P, n2] sorted per row ->
+ *                          wpp[s] = int_0^1 |F_u^-1(q) - F_v^-1(q)|^p dq   (fp64)
+ *                        for the uniform-weight empirical measures of row s: mean_i |u_i - v_i|^p for n1 == n2, else the sum
+ *                        over the merged quantile breakpoints with weights formed exactly in int64 (n1 * n2 < 2^63), and
+ *                          dist[0] = (sum_s wpp[s] / P)^(1/p)   (fp32).
+ *                        p >= 1 real (fast paths for 1 and 2).  A NaN anywhere in a row makes that wpp and dist NaN.
+ *                        partial = mf_swd_cost_ws_doubles(P, n1, n2) doubles of scratch.                                    */
+int mf_swd_project(const float* x, int64_t n, int d, const float* dir, int P, float* u, void* stream);
+int64_t mf_segsort_workspace_bytes(int P, int64_t n, int tile_log2);
+int mf_segsort_f32(const float* keys, int P, int64_t n, int tile_log2, float* out, void* ws, void* stream);
+int64_t mf_swd_cost_ws_doubles(int P, int64_t n1, int64_t n2);
+int mf_swd_quantile_cost(const float* u, int64_t n1, const float* v, int64_t n2, int P, float p, double* partial, double* wpp,
+                         float* dist, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,13 +2,15 @@
 
 Same public names as the reference package ``mentflow`` for the hot path:
 ``MENTFlow``, ``generate``, ``simulate``, ``diagnostics``, ``entropy``, ``prior``, ``loss``, ``train``, ``utils``, and the
-classical MENT solver: ``ment``, ``sample`` (``train.MENTTrainer``).
+classical MENT solver: ``ment``, ``sample`` (``train.MENTTrainer``); ``evaluate.Evaluator`` is the reference's per-experiment
+``setup_eval`` as one class.
 Compute = hand-written HIP kernels behind the C ABI in include/mentflow_hip.h; no CPU fallback.
 """
 from .core import MENTFlow
 from . import diagnostics
 from . import dist
 from . import entropy
+from . import evaluate
 from . import generate
 from . import graph
 from . import loss
@@ -19,4 +21,5 @@ from . import sample
 from . import simulate
 from . import train
 from . import utils
+from .evaluate import Evaluator
 from .utils import unravel

@@ -1,5 +1,10 @@
-"""Discrepancy functions — mirrors mentflow/loss.py:7-17 (SlicedWassersteinDistance, an eval-only metric on a
-third-party OT solver, is out of scope: SURVEY.md §2 row 8)."""
+"""Discrepancy functions and the sliced Wasserstein distance — mirrors mentflow/loss.py:7-42.
+
+The reference hands the sorted-quantile cost of each projection to POT's CPU solver (``ot.lp.wasserstein_1d``); here the
+projections, a segmented key sort and the quantile integral are HIP kernels (mentflow_amd/csrc/swd.hip), and the
+distance comes back as a 0-dim device tensor without a device-to-host copy.  Evaluation only: it is not differentiable."""
+from typing import Optional
+
 import torch
 
 from . import ops
@@ -28,3 +33,47 @@ def kl_divergence(pred: torch.Tensor, targ: torch.Tensor, pad=1.00e-12) -> torch
 kl_divergence.kind = "kld"
 mean_absolute_error.kind = "mae"
 mean_square_error.kind = "mse"
+
+
+class SlicedWassersteindDistance:
+    """Sliced Wasserstein Distance (SWD), loss.py:20-42 (the class name keeps the reference's spelling).
+
+    ``(mean over n_projections random unit directions of W_p^p(x1 . dir, x2 . dir))^(1/p)`` for the uniform-weight empirical
+    measures of x1[N1, d] and x2[N2, d] (N1 != N2 allowed, d <= 8).  The directions are drawn as the reference draws them
+    (``torch.randn(d, n_projections, device=...)``, columns normalised), so ``torch.manual_seed`` fixes the value; the
+    keyword-only ``directions[d, P]`` replaces the draw (same slices for two models, tests).  A NaN in an input gives NaN."""
+
+    def __init__(self, n_projections: int = 50, p: int = 2, device=None) -> None:
+        self.n_projections = n_projections
+        self.p = p
+        self.device = device
+
+    def __call__(self, x1: torch.Tensor, x2: torch.Tensor, *, directions: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if x1.dim() != 2 or x2.dim() != 2:
+            raise ValueError(f"x1 and x2 must be [N, d] point clouds (got {tuple(x1.shape)}, {tuple(x2.shape)})")
+        if x1.shape[1] != x2.shape[1]:
+            raise ValueError(f"x1.shape[1]={x1.shape} != x2.shape[1]={x2.shape})")
+        if torch.is_grad_enabled() and (x1.requires_grad or x2.requires_grad):
+            raise NotImplementedError("SlicedWassersteinDistance is an evaluation metric without a backward pass: call it under "
+                                      "torch.no_grad() or on detached samples")
+        d = x1.shape[1]
+        if x1.shape[0] == 0 or x2.shape[0] == 0:
+            raise ValueError(f"x1 and x2 need at least one point each (got {x1.shape[0]}, {x2.shape[0]})")
+        if d < 1 or d > 8:
+            raise ValueError(f"the projection kernels support 1 <= d <= 8 features (got {d})")
+        if not float(self.p) >= 1.0:
+            raise ValueError(f"p must be >= 1 (got {self.p})")
+        if directions is None:
+            if int(self.n_projections) < 1:
+                raise ValueError(f"n_projections must be positive (got {self.n_projections})")
+            directions = torch.randn(d, self.n_projections, device=self.device)
+            directions = directions / torch.sqrt(torch.sum(directions**2, 0, keepdims=True))
+        elif directions.dim() != 2 or directions.shape[0] != d or directions.shape[1] < 1:
+            raise ValueError(f"directions must be [d={d}, P >= 1] (got {tuple(directions.shape)})")
+        if directions.shape[1] * max(x1.shape[0], x2.shape[0]) >= 2**31:
+            raise ValueError(f"{directions.shape[1]} projections of {max(x1.shape[0], x2.shape[0])} points reach 2^31 keys")
+        directions = directions.detach().to(x1.device, torch.float32)
+        return ops.sliced_wasserstein(x1.detach(), x2.detach(), directions, float(self.p))
+
+
+SlicedWassersteinDistance = SlicedWassersteindDistance

@@ -545,3 +545,66 @@ def ment_integrate(minv: torch.Tensor, coords: List[torch.Tensor], meas_axes, de
          desc.shape[0], ptr(desc), ptr(meta), ptr(tables), tables.numel(), int(prior[0]), float(prior[1]), float(prior[2]),
          ptr(partial), ptr(pred), stream_ptr(cat))
     return pred
+
+
+# ------------------------------------------------------------------------------------------------ sliced Wasserstein distance
+# Thin wrappers over mf_swd_* / mf_segsort_* (include/mentflow_hip.h).  Evaluation only: nothing here is differentiable.
+def swd_project(x: torch.Tensor, directions: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """u[P, N] = (x[N, d] @ directions[d, P]).T, projection-major: each projection is one contiguous segment."""
+    x, directions = _f32c(x), _f32c(directions)
+    if x.dim() != 2 or directions.dim() != 2 or directions.shape[0] != x.shape[1]:
+        raise ValueError(f"swd_project: x[N, d] and directions[d, P] expected (got {tuple(x.shape)}, {tuple(directions.shape)})")
+    P, n = directions.shape[1], x.shape[0]
+    if out is None:
+        out = torch.empty(P, n, dtype=_F32, device=x.device)
+    call("mf_swd_project", ptr(x), n, x.shape[1], ptr(directions), P, ptr(out), stream_ptr(x))
+    return out
+
+
+def segmented_sort(keys: torch.Tensor, out: Optional[torch.Tensor] = None, _tile_log2: int = 0) -> torch.Tensor:
+    """Each row of keys[P, N] in ascending order (torch.sort's convention: NaN last); `out` may be `keys`.  _tile_log2 is a
+    private override of the LDS tile (tests reach the multi-tile merge passes with a few thousand keys through it)."""
+    keys = _f32c(keys)
+    if keys.dim() != 2:
+        raise ValueError(f"segmented_sort: keys[P, N] expected (got {tuple(keys.shape)})")
+    P, n = keys.shape
+    if out is None:
+        out = torch.empty_like(keys)
+    nbytes = int(_lib.get_lib().mf_segsort_workspace_bytes(P, n, int(_tile_log2)))
+    ws = torch.empty(nbytes // 4, dtype=torch.int32, device=keys.device) if nbytes > 0 else None
+    call("mf_segsort_f32", ptr(keys), P, n, int(_tile_log2), ptr(out), ptr(ws), stream_ptr(keys))
+    return out
+
+
+def swd_quantile_cost(u: torch.Tensor, v: torch.Tensor, p: float = 2.0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(wpp[P] fp64, dist 0-dim fp32) of row-wise SORTED u[P, N1], v[P, N2]: wpp = W_p^p of the two uniform-weight empirical
+    measures per row, dist = (mean wpp)^(1/p)."""
+    u, v = _f32c(u), _f32c(v)
+    if u.dim() != 2 or v.dim() != 2 or u.shape[0] != v.shape[0]:
+        raise ValueError(f"swd_quantile_cost: u[P, N1] and v[P, N2] expected (got {tuple(u.shape)}, {tuple(v.shape)})")
+    P = u.shape[0]
+    nws = int(_lib.get_lib().mf_swd_cost_ws_doubles(P, u.shape[1], v.shape[1]))
+    partial = torch.empty(max(1, nws), dtype=torch.float64, device=u.device)
+    wpp = torch.empty(P, dtype=torch.float64, device=u.device)
+    dist = torch.empty((), dtype=_F32, device=u.device)
+    call("mf_swd_quantile_cost", ptr(u), u.shape[1], ptr(v), v.shape[1], P, float(p), ptr(partial), ptr(wpp), ptr(dist),
+         stream_ptr(u))
+    return wpp, dist
+
+
+def sliced_wasserstein(x1: torch.Tensor, x2: torch.Tensor, directions: torch.Tensor, p: float = 2.0) -> torch.Tensor:
+    """(mean over the columns of directions[d, P] of W_p^p(x1 . dir, x2 . dir))^(1/p) as a 0-dim fp32 device tensor; no
+    device-to-host copy.  Equal sizes: both clouds are projected into one [2P, N] buffer and sorted by one launch sequence."""
+    P = directions.shape[1]
+    if x1.shape[0] == x2.shape[0]:
+        u = torch.empty(2 * P, x1.shape[0], dtype=_F32, device=x1.device)
+        swd_project(x1, directions, out=u[:P])
+        swd_project(x2, directions, out=u[P:])
+        segmented_sort(u, out=u)
+        u1, u2 = u[:P], u[P:]
+    else:
+        u1 = swd_project(x1, directions)
+        u2 = swd_project(x2, directions)
+        segmented_sort(u1, out=u1)
+        segmented_sort(u2, out=u2)
+    return swd_quantile_cost(u1, u2, p)[1]
