@@ -5,6 +5,7 @@ measurements, thin sextupole kick of strength -1.5 ... +1.5 followed by a 90-deg
 
     python examples/train_rec_2d_nonlinear.py --gen nsf        # flow: MC entropy + KL
     python examples/train_rec_2d_nonlinear.py --gen nn         # plain network: no entropy term, MAE
+    python examples/train_rec_2d_nonlinear.py --gen nn --entropy knn     # plain network, L = H + mu D with the k-NN entropy
 """
 import argparse
 import os
@@ -25,13 +26,16 @@ def main():
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--batch-size", type=int, default=40000)
     ap.add_argument("--seed", type=int, default=21)
+    ap.add_argument("--entropy", default="none", choices=["none", "cov", "knn"],
+                    help="sample-based entropy estimator; 'none' keeps the configuration's own (MC for the flow, none for nn)")
     args = ap.parse_args()
 
     dev = torch.device("cuda", 0)
     nn_gen = args.gen == "nn"
     prob = build_problem(ndim=2, num=4, bins=85, xmax=4.5, seed=args.seed, transforms=5, prior_scale=1.0, device=dev,
                          dist_name="rings", meas_samples=1_000_000, optics="2d_nonlinear", gen_name=args.gen,
-                         hidden_layers=3, hidden_units=50 if nn_gen else 64, discrepancy="mae" if nn_gen else "kld")
+                         hidden_layers=3, hidden_units=50 if nn_gen else 64, discrepancy="mae" if nn_gen else "kld",
+                         entropy_estimator=None if args.entropy == "none" else args.entropy)
     model = prob.model
     torch.manual_seed(args.seed)
     opt = torch.optim.AdamW(model.parameters(), lr=1e-3 if not nn_gen else 1e-2, weight_decay=0.0)

@@ -327,6 +327,37 @@ int64_t mf_swd_cost_ws_doubles(int P, int64_t n1, int64_t n2);
 int mf_swd_quantile_cost(const float* u, int64_t n1, const float* v, int64_t n2, int P, float p, double* partial, double* wpp,
                          float* dist, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Sample-based entropy estimators  (mentflow/entropy.py:27-50).  Purely additive entry points: MF_ABI_VERSION stays 5.  Both
+ * return the NEGATIVE entropy H as one fp32 device scalar; no float atomics, fp64 sums in a fixed order: every output is
+ * bitwise reproducible.  x[n, d] fp32, 1 <= d <= 16.
+ *
+ * mf_knn_entropy_fwd:  Kozachenko-Leonenko estimate with the k-th nearest other point, 1 <= k <= 16, n > k:
+ *                        H = -[psi(n) - psi(k) + ln c_d + (d / n) sum_i ln rho_k(i)],   c_d = pi^(d/2) / Gamma(d/2 + 1).
+ *                      rho^2 from direct fp32 differences; neighbours ordered by (rho^2, index); ln rho = 0.5 ln max(rho^2,
+ *                      FLT_MIN).  Outputs: H[1], sum_ln_rho[1] (fp64), idx[n] (the k-th neighbour j(i), always in [0, n)) and
+ *                      rho2[n].  A point with fewer than k candidates at finite distance (NaN / inf coordinates) gets
+ *                      rho2 = +inf and idx = i, which makes H non-finite.  `chunks` cuts the candidate range over the grid
+ *                      (0: built-in choice, else 1..65535); idx and rho2 do not depend on it.
+ *                      ws = mf_knn_entropy_ws_bytes(n, d, k, chunks) bytes of device scratch (-1: bad arguments).
+ * mf_knn_entropy_bwd:  gx[i] = coef[0] * cscale * d(sum ln rho)/dx_i
+ *                            = coef[0] * cscale * [ w_i (x_i - x_j(i)) + sum_{i': j(i') = i} w_i' (x_i - x_i') ],
+ *                      w = 1 / rho2 where FLT_MIN < rho2 < inf, else 0; the reverse-neighbour sum runs in ascending i'.  coef is
+ *                      a DEVICE scalar (the upstream gradient); the caller passes cscale = -d / n.
+ * mf_cov_entropy_fwd:  eps = sqrt(det(cov(x))) (divisor n - 1), H = -3 ln(2 pi e) - ln(eps + pad): the reference's formula as it
+ *                      stands (its constant is the 6-D one whatever d).  aux[d + d * d] (fp64) receives the mean and the matrix
+ *                      A = -eps / (eps + pad) / (n - 1) * cov^-1 of the adjoint (zero where det is not positive and finite).
+ *                      ws = mf_cov_entropy_ws_doubles(n, d) doubles of device scratch (-1: bad arguments).
+ * mf_cov_entropy_bwd:  gx[i] = coef[0] * A (x_i - mean), evaluated in fp64 and rounded once.                              */
+int64_t mf_knn_entropy_ws_bytes(int64_t n, int d, int k, int chunks);
+int mf_knn_entropy_fwd(const float* x, int64_t n, int d, int k, int chunks, float* H, double* sum_ln_rho, int32_t* idx,
+                       float* rho2, void* ws, void* stream);
+int mf_knn_entropy_bwd(const float* x, int64_t n, int d, const int32_t* idx, const float* rho2, const float* coef,
+                       float cscale, float* gx, void* stream);
+int64_t mf_cov_entropy_ws_doubles(int64_t n, int d);
+int mf_cov_entropy_fwd(const float* x, int64_t n, int d, double pad, float* H, double* aux, double* ws, void* stream);
+int mf_cov_entropy_bwd(const float* x, int64_t n, int d, const double* aux, const float* coef, float* gx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

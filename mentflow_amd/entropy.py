@@ -26,6 +26,41 @@ class EmptyEntropyEstimator(EntropyEstimator):
         return 0.0
 
 
+class CovarianceEntropyEstimator(EntropyEstimator):
+    """H = -3 ln(2 pi e) - ln(sqrt(det cov(x)) + pad)  (entropy.py:27-38): the negative entropy of the Gaussian with the
+    samples' covariance.  The constant is the reference's as it stands, -3 ln(2 pi e) for EVERY dimension (it is the 6-D
+    value -(d/2) ln(2 pi e)); it is reproduced, not corrected, and shifts H only.  Moments, determinant, inverse and the
+    adjoint run on the GPU without a host synchronisation (ops.CovEntropyFn)."""
+
+    def __init__(self, prior: Any = None, pad: float = 1.00e-12) -> None:
+        if prior is not None:
+            raise ValueError("This class cannot estimate relative entropy (prior != None).")
+        super().__init__(prior=prior)
+        self.pad = pad
+
+    def forward(self, x: torch.Tensor, log_prob: Optional[torch.Tensor] = None) -> torch.Tensor:
+        return ops.cov_entropy(x, self.pad)
+
+
+class KNNEntropyEstimator(EntropyEstimator):
+    """Kozachenko-Leonenko estimate from the k-th nearest other point of the batch (the reference declares the class,
+    entropy.py:41-50, and leaves forward unimplemented):
+
+        H = -[psi(N) - psi(k) + ln c_d + (d / N) sum_i ln rho_k(i)],   c_d = pi^(d/2) / Gamma(d/2 + 1)
+
+    differentiable in x.  1 <= k <= 16, N > k, 1 <= d <= 16, float32 on the GPU; all-pairs search without an N x N buffer
+    (ops.KnnEntropyFn, DESIGN.md §6d for the tie-break, floor and non-finite rules)."""
+
+    def __init__(self, prior: Any = None, k: int = 5) -> None:
+        if prior is not None:
+            raise ValueError("This class cannot estimate relative entropy (prior != None).")
+        super().__init__(prior=prior)
+        self.k = k
+
+    def forward(self, x: torch.Tensor, log_prob: Optional[torch.Tensor] = None) -> torch.Tensor:
+        return ops.knn_entropy(x, self.k)[0]
+
+
 class MonteCarloEntropyEstimator(EntropyEstimator):
     """H = mean(log_prob) - mean(prior.log_prob(x))  (entropy.py:53-62), both means from one reduction kernel.
 

@@ -130,8 +130,12 @@ def build_problem(ndim: int = 6, num: int = 25, bins: int = 64, xmax: float = 4.
                   transforms: int = 5, prior_scale: float = 1.0, device="cuda", dist_name: str = "rings",
                   dist_kws: Optional[dict] = None, meas_samples: int = 1_000_000, gen_name: str = "nsf",
                   hidden_layers: int = 3, hidden_units: int = 64, spline_bins: int = 20, optics: str = "nd_1d",
-                  bandwidth: float = 0.5, discrepancy: str = "kld", penalty_parameter: float = 0.0) -> Problem:
-    """generate_training_data + setup_mentflow_model (experiments/setup.py:21-151) for the BASELINE workloads."""
+                  bandwidth: float = 0.5, discrepancy: str = "kld", penalty_parameter: float = 0.0,
+                  entropy_estimator: Optional[str] = None) -> Problem:
+    """generate_training_data + setup_mentflow_model (experiments/setup.py:21-151) for the BASELINE workloads.
+    entropy_estimator: None = the configuration's own choice ("none" for the NN generator, "mc" for the flows), else "none" |
+    "mc" | "cov" | "knn" as in get_entropy_estimator (setup.py:91-97); "cov" and "knn" estimate the absolute entropy
+    (prior=None)."""
     device = torch.device(device)
     if seed is not None:
         torch.manual_seed(seed)                                           # setup.py:35-36
@@ -171,7 +175,18 @@ def build_problem(ndim: int = 6, num: int = 25, bins: int = 64, xmax: float = 4.
     prior = mfp.Gaussian(ndim=ndim, scale=prior_scale, device=device)     # setup.py:133-135
     disc = {"kld": mfl.kl_divergence, "mae": mfl.mean_absolute_error, "mse": mfl.mean_square_error}[discrepancy]
     # config/model/nn.yaml: entropy_estimator "none" for the density-free NN generator (setup.py:137-141)
-    estimator = mfe.EmptyEntropyEstimator() if gen_name == "nn" else mfe.MonteCarloEntropyEstimator(prior=prior)
+    if entropy_estimator is None:
+        estimator = mfe.EmptyEntropyEstimator() if gen_name == "nn" else mfe.MonteCarloEntropyEstimator(prior=prior)
+    elif entropy_estimator == "none":
+        estimator = mfe.EmptyEntropyEstimator()
+    elif entropy_estimator == "mc":
+        estimator = mfe.MonteCarloEntropyEstimator(prior=prior)
+    elif entropy_estimator == "cov":
+        estimator = mfe.CovarianceEntropyEstimator(prior=None)
+    elif entropy_estimator == "knn":
+        estimator = mfe.KNNEntropyEstimator(prior=None)
+    else:
+        raise ValueError(f"Invalid entropy estimator '{entropy_estimator}'")
     model = MENTFlow(generator=generator, entropy_estimator=estimator, prior=prior,
                      transforms=tfs, diagnostics=diagnostics, measurements=measurements,
                      penalty_parameter=penalty_parameter, discrepancy_function=disc)

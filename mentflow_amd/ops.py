@@ -446,6 +446,80 @@ class EntropySumsFn(torch.autograd.Function):
         return gx, glogp
 
 
+class KnnEntropyFn(torch.autograd.Function):
+    """x[N,d] -> (H, idx[N], rho2[N], sum ln rho): the Kozachenko-Leonenko negative entropy with the k-th nearest other point
+    (include/mentflow_hip.h, mf_knn_entropy_*).  Only H is differentiable.  chunks = 0: the built-in cut of the candidate
+    range over the grid."""
+
+    @staticmethod
+    def forward(ctx, x, k: int, chunks: int):
+        x = _f32c(x)
+        if x.dim() != 2:
+            raise ValueError(f"knn_entropy: x[N, d] expected (got {tuple(x.shape)})")
+        n, d = x.shape
+        ptr(x)                                             # a CPU tensor is refused before anything is allocated for it
+        nbytes = int(_lib.get_lib().mf_knn_entropy_ws_bytes(n, d, int(k), int(chunks)))
+        if nbytes < 0:
+            raise RuntimeError(f"mf_knn_entropy_ws_bytes failed: {_lib.get_lib().mf_last_error().decode()}")
+        ws = torch.empty(nbytes // 8, dtype=torch.float64, device=x.device)
+        H = torch.empty((), dtype=_F32, device=x.device)
+        S = torch.empty((), dtype=torch.float64, device=x.device)
+        idx = torch.empty(n, dtype=torch.int32, device=x.device)
+        rho2 = torch.empty(n, dtype=_F32, device=x.device)
+        call("mf_knn_entropy_fwd", ptr(x), n, d, int(k), int(chunks), ptr(H), ptr(S), ptr(idx), ptr(rho2), ptr(ws),
+             stream_ptr(x))
+        ctx.save_for_backward(x, idx, rho2)
+        ctx.mark_non_differentiable(idx, rho2, S)
+        return H, idx, rho2, S
+
+    @staticmethod
+    def backward(ctx, gH, _gidx, _grho2, _gS):
+        x, idx, rho2 = ctx.saved_tensors
+        n, d = x.shape
+        gx = torch.empty_like(x)
+        call("mf_knn_entropy_bwd", ptr(x), n, d, ptr(idx), ptr(rho2), ptr(_f32c(gH).reshape(1)), -float(d) / float(n), ptr(gx),
+             stream_ptr(x))
+        return gx, None, None
+
+
+def knn_entropy(x: torch.Tensor, k: int = 5, _chunks: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(H, idx, rho2, sum_ln_rho) of KnnEntropyFn.  _chunks is a private override of the number of candidate chunks (tests
+    reach the multi-chunk merge with a few thousand points through it); idx and rho2 do not depend on it."""
+    return KnnEntropyFn.apply(x, int(k), int(_chunks))
+
+
+class CovEntropyFn(torch.autograd.Function):
+    """x[N,d] -> H = -3 ln(2 pi e) - ln(sqrt(det cov x) + pad)  (entropy.py:35-38; mf_cov_entropy_*)."""
+
+    @staticmethod
+    def forward(ctx, x, pad: float):
+        x = _f32c(x)
+        if x.dim() != 2:
+            raise ValueError(f"cov_entropy: x[N, d] expected (got {tuple(x.shape)})")
+        n, d = x.shape
+        ptr(x)
+        nws = int(_lib.get_lib().mf_cov_entropy_ws_doubles(n, d))
+        if nws < 0:
+            raise RuntimeError(f"mf_cov_entropy_ws_doubles failed: {_lib.get_lib().mf_last_error().decode()}")
+        ws = torch.empty(nws, dtype=torch.float64, device=x.device)
+        aux = torch.empty(d + d * d, dtype=torch.float64, device=x.device)
+        H = torch.empty((), dtype=_F32, device=x.device)
+        call("mf_cov_entropy_fwd", ptr(x), n, d, float(pad), ptr(H), ptr(aux), ptr(ws), stream_ptr(x))
+        ctx.save_for_backward(x, aux)
+        return H
+
+    @staticmethod
+    def backward(ctx, gH):
+        x, aux = ctx.saved_tensors
+        gx = torch.empty_like(x)
+        call("mf_cov_entropy_bwd", ptr(x), x.shape[0], x.shape[1], ptr(aux), ptr(_f32c(gH).reshape(1)), ptr(gx), stream_ptr(x))
+        return gx, None
+
+
+def cov_entropy(x: torch.Tensor, pad: float = 1.0e-12) -> torch.Tensor:
+    return CovEntropyFn.apply(x, float(pad))
+
+
 def proj_hist_counts_1d(x, V, edges) -> torch.Tensor:
     x, V, edges = _f32c(x), _f32c(V), _f32c(edges)
     P, B = V.shape[0], edges.numel() - 1
