@@ -301,6 +301,27 @@ int mf_ment_integrate(int d, const float* minv, const float* coords, const int64
                       float* pred, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Metropolis-Hastings chains on the density of classical MENT (no counterpart in the reference).  A purely additive entry
+ * point: MF_ABI_VERSION stays 5.  Slot arguments (nslot .. prior_lognorm) exactly as mf_ment_prob takes them.
+ *
+ * mf_mcmc_ment_steps: `chains` independent random-walk chains, one GPU lane each, advance `steps` steps from x[chains, d]
+ *                     (in / out).  Step t of the call has the global index g = step_offset + t:
+ *                       y = fma(scale[a], noise[t][a][c], x[a]) for a < d,  p_new = prob(y) (the bits mf_ment_prob returns),
+ *                       u = noise[t][d][c];  accept iff  p_new > 0 ? u * p < p_new : (p_new == 0 && p == 0),
+ *                     so a chain never leaves the support once inside, random-walks while outside it, and rejects a NaN
+ *                     p_new or u.  p = prob(x) is recomputed at entry.  noise[steps][d + 1][chains] (chain fastest; the caller
+ *                     draws normal rows 0..d-1 and a uniform [0, 1) row d), scale[d] on the DEVICE.  If g >= keep_from and
+ *                     (g - keep_from) % keep_every == 0 the state after step g is written to
+ *                     out[(g - keep_from) / keep_every][c][0..d); out may be NULL (nothing kept).  accepted[c] (int32) is
+ *                     incremented by the chain's accepted proposals.  No atomics; chains do not interact; the outputs are
+ *                     bitwise reproducible and do not depend on how a run is cut into calls (step_offset advanced).
+ *                     keep_every >= 1; steps, step_offset, keep_from, keep_every <= 2^40.                                    */
+int mf_mcmc_ment_steps(float* x, int64_t chains, int d, int nslot, const float* desc, const int32_t* meta, const float* tables,
+                       int64_t table_floats, int prior_kind, float prior_a, float prior_lognorm, const float* noise,
+                       int64_t steps, int64_t step_offset, const float* scale, int64_t keep_from, int64_t keep_every,
+                       float* out, int32_t* accepted, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Sliced Wasserstein distance  (mentflow/loss.py:20-42, where the 1-D transport cost is POT's ot.lp.wasserstein_1d on the
  * host).  Purely additive entry points: MF_ABI_VERSION stays 5.  No float atomics, fp64 sums in a fixed order: every output
  * is bitwise reproducible.  All sizes obey P * n < 2^31.

@@ -361,11 +361,19 @@ class MENT:
     def prob_on_grid(self, coords: List[torch.Tensor]):
         """(prob, block sums) on the implicit tensor grid of the cell centres `coords` (GridSampler's fast path), or None
         when a slot runs outside the kernels."""
-        if len(coords) != self.ndim or not self.fully_fused():
+        args = self.fused_args()
+        if len(coords) != self.ndim or args is None:
+            return None
+        coords = [c.to(self._device(), torch.float32) for c in coords]
+        return ops.ment_prob_grid(coords, *args)
+
+    def fused_args(self):
+        """(desc, meta, tables, prior args) of the one kernel chain whose product is exactly ``prob`` (what the implicit-grid
+        and Metropolis-Hastings kernels take), or None when a slot runs outside the kernels."""
+        if not self.fully_fused():
             return None
         chain = self._get_plan()[0][0]
-        coords = [c.to(self._device(), torch.float32) for c in coords]
-        return ops.ment_prob_grid(coords, chain.desc_t, chain.meta_t, self._tables(chain), _prior_args(self.prior))
+        return chain.desc_t, chain.meta_t, self._tables(chain), _prior_args(self.prior)
 
     def sample(self, size: int) -> torch.Tensor:
         return self.send(self.sampler(self.prob, size))

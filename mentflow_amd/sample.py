@@ -11,14 +11,20 @@ the block sums.
 
 Quirk kept from the reference: with ``noise`` truthy every axis also gets ``0.5 U(-delta, delta)``, whatever the value of
 ``noise`` (sample.py:58-60).
+
+``MetropolisHastingsSampler`` (no counterpart in the reference) draws particles from many independent random-walk
+Metropolis-Hastings chains instead: it needs point evaluations of the density only, so its cost does not grow as res^ndim.
+Same call contract as ``GridSampler``; kernel in mentflow_amd/csrc/mcmc.hip.
 """
 from __future__ import annotations
 
-from typing import Callable, List, Tuple
+import logging
+import math
+from typing import Callable, List, Optional, Sequence, Tuple, Union
 
 import torch
 
-from . import ops
+from . import _lib, ops
 from .utils import coords_from_edges, get_grid_points
 
 
@@ -105,3 +111,148 @@ class GridSampler:
         if self.points is not None:
             self.points = self.send(self.points)
         return self
+
+
+log = logging.getLogger("mentflow_amd.sample")
+_NOISE_CHUNK_BYTES = 256 << 20      # noise of one launch of the fused path (generated per chunk, never for the whole run)
+
+
+class MetropolisHastingsSampler:
+    """`chains` independent random-walk Metropolis-Hastings chains on a density given by point evaluations.
+
+    One step of a chain at x with density p: y = x + step * z (z standard normal per axis), p_new = prob(y), u uniform on
+    [0, 1); accept iff ``p_new > 0 ? u * p < p_new : (p_new == 0 and p == 0)``.  Inside the support that is the Metropolis rule;
+    a chain outside it (p == 0) random-walks until it finds it and never leaves it again; a NaN p_new is rejected.  The noise
+    is ``torch.randn`` / ``torch.rand`` on the device, so ``torch.manual_seed`` fixes a run.
+
+    Called with ``MENT.prob`` itself of a MENT whose slots all run through the kernels, the steps run in the fused kernel
+    (state and density in registers, one launch per chunk of steps); any other callable (``log_prob`` is NOT a density, a
+    subclass's override, a user function) takes the same rule in torch ops with one ``prob_func`` call per step, logged once.
+
+    ``sampler(prob_func, size)`` runs ``burn + ceil(size / chains) * thin`` steps, keeps every ``thin``-th state after the burn-in
+    and returns the first ``size`` rows of the kept block (step-major).  With ``persistent`` later calls continue from the stored
+    states and burn only ``burn_persistent`` (default ``thin``) steps: between Gauss-Seidel sub-steps the density moves little.
+    """
+
+    def __init__(self, ndim: int, chains: int = 65536, step: Union[float, Sequence[float]] = 0.25, burn: int = 200,
+                 thin: int = 10, start: Optional[torch.Tensor] = None, start_scale: float = 1.0, persistent: bool = True,
+                 burn_persistent: Optional[int] = None, device: torch.device = None) -> None:
+        self.ndim, self.chains = int(ndim), int(chains)
+        if not 1 <= self.ndim <= 8:
+            raise ValueError(f"MetropolisHastingsSampler: 1 <= ndim <= 8 expected (got {ndim})")
+        if self.chains < 1 or int(burn) < 0 or int(thin) < 1:
+            raise ValueError("MetropolisHastingsSampler: chains >= 1, burn >= 0 and thin >= 1 expected")
+        self.step = [float(step)] * self.ndim if isinstance(step, (int, float)) else [float(v) for v in step]
+        if len(self.step) != self.ndim:
+            raise ValueError(f"MetropolisHastingsSampler: step must be a float or {self.ndim} per-axis scales (got {len(self.step)})")
+        if start is not None and tuple(start.shape) != (self.chains, self.ndim):
+            raise ValueError(f"MetropolisHastingsSampler: start[{self.chains}, {self.ndim}] expected (got {tuple(start.shape)})")
+        self.burn, self.thin = int(burn), int(thin)
+        self.start, self.start_scale = start, float(start_scale)
+        self.persistent = bool(persistent)
+        self.burn_persistent = self.thin if burn_persistent is None else int(burn_persistent)
+        self.device = device
+        self.state: Optional[torch.Tensor] = None
+        self.acceptance: Optional[torch.Tensor] = None
+        self._logged_generic = False
+
+    def reset(self) -> None:
+        """Forget the chain states: the next call starts from `start` (or a fresh normal draw) and burns `burn` steps."""
+        self.state = None
+
+    def to(self, device):
+        self.device = device
+        for name in ("start", "state", "acceptance"):
+            t = getattr(self, name)
+            if t is not None:
+                setattr(self, name, t.to(device))
+        return self
+
+    # ---------------------------------------------------------------------------------------------------- internals
+    def _fused_args(self, prob_func: Callable):
+        from .ment import MENT
+        owner = getattr(prob_func, "__self__", None)
+        if isinstance(owner, MENT) and getattr(prob_func, "__func__", None) is MENT.prob:
+            if owner.ndim != self.ndim:
+                raise ValueError(f"MetropolisHastingsSampler(ndim={self.ndim}) called with the density of a MENT of ndim={owner.ndim}")
+            return owner.fused_args()
+        return None
+
+    def _init_state(self, prob_func: Callable) -> None:
+        device = self.device
+        if device is None:
+            owner = getattr(prob_func, "__self__", None)
+            device = owner._device() if hasattr(owner, "_device") else torch.device(_lib.device_type())
+        if self.start is not None:
+            self.state = self.start.detach().to(device, torch.float32).clone().contiguous()
+        else:
+            self.state = self.start_scale * torch.randn(self.chains, self.ndim, device=device)
+
+    def _noise(self, steps: int, device) -> torch.Tensor:
+        nz = torch.empty(steps, self.ndim + 1, self.chains, device=device)
+        nz[:, :self.ndim].normal_()
+        nz[:, self.ndim].uniform_()
+        return nz
+
+    def _generic_steps(self, prob_func, noise, scale, accepted, t0, keep_from, keep_every, out) -> None:
+        x, d = self.state, self.ndim
+        p = prob_func(x)
+        for t in range(noise.shape[0]):
+            # the kernel's fma(scale, z, x): the fp32 product is exact in fp64, so this differs from it by a double rounding at most
+            y = (x.double() + noise[t, :d].T.double() * scale.double()).float()
+            p_new = prob_func(y)
+            accept = torch.where(p_new > 0, noise[t, d] * p < p_new, (p_new == 0) & (p == 0))
+            x = torch.where(accept[:, None], y, x)
+            p = torch.where(accept, p_new, p)
+            accepted += accept.to(torch.int32)
+            k = t0 + t - keep_from
+            if out is not None and k >= 0 and k % keep_every == 0:
+                out[k // keep_every] = x
+        self.state = x.contiguous()
+
+    def run(self, prob_func: Callable, steps: int, noise: Optional[torch.Tensor] = None, keep_from: int = 0,
+            keep_every: int = 1) -> torch.Tensor:
+        """Advance every chain by `steps` steps and return the states after the steps g >= keep_from with
+        (g - keep_from) % keep_every == 0 as [n_keep, chains, ndim].  noise: [steps, ndim + 1, chains] (normal proposal rows,
+        a uniform last row), default drawn on the device in chunks."""
+        steps, keep_from, keep_every = int(steps), int(keep_from), int(keep_every)
+        if steps < 0 or keep_from < 0 or keep_every < 1:
+            raise ValueError("MetropolisHastingsSampler.run: steps, keep_from >= 0 and keep_every >= 1 expected")
+        args = self._fused_args(prob_func)
+        if self.state is None:
+            self._init_state(prob_func)
+        x = self.state
+        _lib.ptr(x)                                            # the usual refusal of tensors the library does not compute on
+        if noise is not None:
+            if tuple(noise.shape) != (steps, self.ndim + 1, self.chains):
+                raise ValueError(f"MetropolisHastingsSampler.run: noise[{steps}, {self.ndim + 1}, {self.chains}] expected "
+                                 f"(got {tuple(noise.shape)})")
+            noise = noise.to(x.device, torch.float32).contiguous()
+        if args is None and not self._logged_generic:
+            self._logged_generic = True
+            log.info("MetropolisHastingsSampler: %s is not the bound MENT.prob of a fully fused MENT: the generic path runs (the "
+                     "same transition rule in torch ops, one density call per step)", getattr(prob_func, "__qualname__", prob_func))
+        n_keep = 0 if steps <= keep_from else (steps - 1 - keep_from) // keep_every + 1
+        out = torch.empty(n_keep, self.chains, self.ndim, device=x.device) if n_keep else None
+        accepted = torch.zeros(self.chains, dtype=torch.int32, device=x.device)
+        scale = torch.tensor(self.step, dtype=torch.float32, device=x.device)
+        per = max(1, _NOISE_CHUNK_BYTES // (4 * (self.ndim + 1) * self.chains))
+        for t0 in range(0, steps, per):
+            t1 = min(steps, t0 + per)
+            nz = noise[t0:t1] if noise is not None else self._noise(t1 - t0, x.device)
+            if args is not None:
+                ops.mcmc_ment_steps(x, args[0], args[1], args[2], args[3], nz, scale, accepted, step_offset=t0,
+                                    keep_from=keep_from, keep_every=keep_every, out=out)
+            else:
+                self._generic_steps(prob_func, nz, scale, accepted, t0, keep_from, keep_every, out)
+        self.acceptance = accepted.sum().to(torch.float32) / float(max(1, steps) * self.chains)
+        return out if out is not None else torch.empty(0, self.chains, self.ndim, device=x.device)
+
+    def __call__(self, prob_func: Callable, size: int) -> torch.Tensor:
+        size = int(size)
+        if not self.persistent:
+            self.reset()
+        burn = self.burn if self.state is None else self.burn_persistent
+        rounds = max(1, math.ceil(size / self.chains))
+        kept = self.run(prob_func, burn + rounds * self.thin, keep_from=burn + self.thin - 1, keep_every=self.thin)
+        return kept.reshape(-1, self.ndim)[:size]
