@@ -1,7 +1,8 @@
 #!/bin/bash
 # TEST INFRASTRUCTURE: builds tests/emu/sanitize_emu — the csrc kernels compiled for the HOST against the fiber
-# emulator with AddressSanitizer + UndefinedBehaviorSanitizer, linked with the driver sanitize_main.cpp (SURVEY.md §5:
-# "sanitizers on the host build").  GPU-side sanitizers are not available on this pool; this is the CPU pass.
+# emulator with AddressSanitizer + UndefinedBehaviorSanitizer, linked with the driver, which is every
+# tests/emu/sanitize_*.cpp (sanitize_main.cpp holds main; SURVEY.md §5: "sanitizers on the host build").  GPU-side
+# sanitizers are not available on this pool; this is the CPU pass.
 set -e
 HERE="$(cd "$(dirname "$0")" && pwd)"
 SRC="$HERE/../../mentflow_amd/csrc"
@@ -24,7 +25,9 @@ while read -r name src flags; do          # one object per line of SOURCES.txt
   esac
 done < "$SRC/SOURCES.txt"
 $CXX -std=c++17 -O1 -g -fPIC -DMF_EMU $SAN -c "$HERE/hip_emu.cpp" -o "$HERE/san/hip_emu.o" &
-$CXX $FLAGS -x c++ -c "$HERE/sanitize_main.cpp" -o "$HERE/san/main.o" &
+for drv in "$HERE"/sanitize_*.cpp; do      # the driver: one object per section, named apart from the kernels' objects
+  $CXX $FLAGS -x c++ -c "$drv" -o "$HERE/san/$(basename "$drv" .cpp).o" &
+done
 wait
 $CXX -fsanitize=address,undefined -o "$HERE/sanitize_emu" "$HERE"/san/*.o
 echo "built $HERE/sanitize_emu"

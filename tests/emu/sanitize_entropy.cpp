@@ -1,36 +1,11 @@
 // TEST INFRASTRUCTURE — NOT PRODUCT CODE.
-// Sanitizer driver for the sample-based entropy estimators (mentflow_amd/csrc/entropy.hip): built by
-// tests/test_entropy_sanitize.py with the flags of tests/emu/build_sanitize.sh (AddressSanitizer + UndefinedBehaviorSanitizer on
-// the fiber emulator), it calls every mf_knn_entropy_* and mf_cov_entropy_* entry point on small synthetic inputs: ragged N
-// (no multiple of the 256-query workgroup, the candidate tile or four), k = 1 and 16, every padded feature count, one and
-// several candidate chunks (also more chunks than tiles), duplicate points, NaN and inf rows, N = k + 1, and the refusals.
-// Every buffer has exactly the documented size, so any out-of-range index or undefined arithmetic aborts.
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-
-#include "../../include/mentflow_hip.h"
-
-static unsigned g_seed = 777u;
-static float urand() {                         // [0, 1)
-    g_seed = g_seed * 1664525u + 1013904223u;
-    return (float)(g_seed >> 8) / 16777216.0f;
-}
-#define CK(call)                                                                 \
-    do {                                                                         \
-        if ((call) != 0) {                                                       \
-            fprintf(stderr, "FAILED %s: %s\n", #call, mf_last_error());          \
-            exit(2);                                                             \
-        }                                                                        \
-    } while (0)
-
-static void check(bool ok, const char* what) {
-    if (!ok) {
-        fprintf(stderr, "check failed: %s\n", what);
-        exit(3);
-    }
-}
+// Entropy-estimator section of the sanitizer driver (mentflow_amd/csrc/entropy.hip).  tests/emu/build_sanitize.sh links it into
+// tests/emu/sanitize_emu (AddressSanitizer + UndefinedBehaviorSanitizer on the fiber emulator), whose main, in
+// sanitize_main.cpp, calls sanitize_entropy().  It calls every mf_knn_entropy_* and mf_cov_entropy_* entry point on small
+// synthetic inputs: ragged N (no multiple of the 256-query workgroup, the candidate tile or four), k = 1 and 16, every padded
+// feature count, one and several candidate chunks (also more chunks than tiles), duplicate points, NaN and inf rows, N = k + 1,
+// and the refusals.  Every buffer has exactly the documented size, so any out-of-range index or undefined arithmetic aborts.
+#include "sanitize_common.h"
 
 static std::vector<float> cloud(int64_t n, int d) {
     std::vector<float> x((size_t)n * d);
@@ -147,9 +122,9 @@ static void cov_cases() {
     check(mf_cov_entropy_bwd(nullptr, 10, 0, nullptr, nullptr, nullptr, nullptr) != 0, "d = 0 refused");
 }
 
-int main() {
+void sanitize_entropy() {
+    seed(777u);
     knn_cases();
     cov_cases();
     printf("SANITIZE ENTROPY OK\n");
-    return 0;
 }

@@ -1,16 +1,19 @@
 // TEST INFRASTRUCTURE — NOT PRODUCT CODE.
-// Sanitizer driver for the host-emulated kernel build: calls every compute entry point of include/mentflow_hip.h on
-// small synthetic inputs.  Built by tests/emu/build_sanitize.sh with -fsanitize=address,undefined (the emulator
-// annotates its fiber switches for ASan and gives every workgroup an exactly-sized, guard-paged dynamic LDS block), so
-// any out-of-range LDS / global index, use of uninitialised stack slots through a pointer, or undefined arithmetic in
-// flow.hip / kde.hip stops the program.   `--provoke-lds-overflow`: self-test of the guard (must crash).
+// Sanitizer driver for the host-emulated kernel build: tests/emu/sanitize_*.cpp together call every compute entry point of
+// include/mentflow_hip.h on small synthetic inputs (tests/test_sanitizers.py checks that against the header).  This file holds
+// main and the flow, KDE and tail sections; sanitize_ment.cpp, sanitize_mcmc.cpp, sanitize_entropy.cpp and sanitize_swd.cpp
+// hold one section each, and sanitize_common.h what they share.  Built by tests/emu/build_sanitize.sh with
+// -fsanitize=address,undefined (the emulator annotates its fiber switches for ASan and gives every workgroup an
+// exactly-sized, guard-paged dynamic LDS block), so any out-of-range LDS / global index, use of uninitialised stack slots
+// through a pointer, or undefined arithmetic in the kernels stops the program.   `--provoke-lds-overflow`: self-test of the
+// guard (must crash).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
-#include "../../include/mentflow_hip.h"
+#include "sanitize_common.h"
 
 static unsigned g_seed = 12345u;
 static float frand() {
@@ -22,13 +25,6 @@ static std::vector<float> rnd(size_t n, float scale) {
     for (auto& x : v) x = scale * 2.0f * frand();
     return v;
 }
-#define CK(call)                                                                 \
-    do {                                                                         \
-        if ((call) != 0) {                                                       \
-            fprintf(stderr, "FAILED %s: %s\n", #call, mf_last_error());          \
-            exit(2);                                                             \
-        }                                                                        \
-    } while (0)
 
 static void all_finite(const std::vector<float>& v, const char* what) {
     for (float x : v)
@@ -112,6 +108,9 @@ static void flow_affine(int d, int L, int64_t n, bool fused) {
 // wide conditioner family (ABI 5): exactly-sized image / scratch / slab buffers, so that a fragment block, a scratch tile or a slab
 // position addressed out of range runs into ASan's redzone
 static void flow_wide(int d, int hidden, int L, int K, int64_t n) {
+    int max_d = 0, max_hidden = 0, max_L = 0;
+    CK(mf_flow_wide_limits(&max_d, &max_hidden, &max_L));
+    check(d <= max_d && hidden <= max_hidden && L <= max_L, "wide case within the limits");
     const int nblk = K ? d : 1;
     const int64_t F = mf_flow_wide_image_floats(L, nblk), G = mf_flow_wide_grad_floats(L, nblk);
     std::vector<float> image = rnd(F, 0.3f);
@@ -273,6 +272,15 @@ int main(int argc, char** argv) {
     kde2d(300, 2, 2, 17, 13, 0.6f, 0.3f, 5, 3);
     tail(1000, 6);
     tail(333, 2);
+    double prof_ms = NAN;                // writes through both pointers (and reports nothing: the emulation records no events)
+    int64_t prof_launches = -1;
+    CK(mf_prof_report(0, &prof_ms, &prof_launches));
+    check(prof_ms == 0.0 && prof_launches == 0, "empty profile");
+    check(mf_flow_set_bwd_variant(2) != 0 && mf_last_error()[0] != '\0', "a refused call leaves its reason");
+    sanitize_ment();
+    sanitize_mcmc();
+    sanitize_entropy();
+    sanitize_swd();
     printf("SANITIZE OK\n");
     return 0;
 }

@@ -1,83 +1,11 @@
 // TEST INFRASTRUCTURE — NOT PRODUCT CODE.
-// Sanitizer driver for the Metropolis-Hastings entry point (mentflow_amd/csrc/mcmc.hip): built by tests/test_mcmc_sanitize.py
-// with the flags of tests/emu/build_sanitize.sh (AddressSanitizer + UndefinedBehaviorSanitizer, the fiber emulator's
-// exactly-sized, guard-paged dynamic LDS), it calls mf_mcmc_ment_steps on small synthetic inputs whose buffers have exactly the
-// documented sizes: tables in LDS and beyond it, d = 1 and d = 8, zero slots, a chain count that is not a multiple of the
-// workgroup, out == NULL, a keep_every that never hits, runs cut into launches, NaN noise, and the refusals.  Any out-of-range
-// index or undefined arithmetic aborts.
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-
-#include "../../include/mentflow_hip.h"
-
-static unsigned g_seed = 777u;
-static float urand() {                         // [0, 1)
-    g_seed = g_seed * 1664525u + 1013904223u;
-    return (float)(g_seed >> 8) / 16777216.0f;
-}
-static float nrand() {                         // roughly normal: a sum of uniforms
-    float s = 0.0f;
-    for (int i = 0; i < 6; ++i) s += urand();
-    return (s - 3.0f) * 1.4142135f;
-}
-#define CK(call)                                                                 \
-    do {                                                                         \
-        if ((call) != 0) {                                                       \
-            fprintf(stderr, "FAILED %s: %s\n", #call, mf_last_error());          \
-            exit(2);                                                             \
-        }                                                                        \
-    } while (0)
-
-static void check(bool ok, const char* what) {
-    if (!ok) {
-        fprintf(stderr, "check failed: %s\n", what);
-        exit(3);
-    }
-}
-
-struct Slots {
-    std::vector<float> desc;
-    std::vector<int32_t> meta;
-    std::vector<float> tables;
-    int n = 0;
-};
-
-// `dims[k]` = 1 or 2 axes, B bins per axis on [-3, 3]: descriptor layout of include/mentflow_hip.h
-static Slots make_slots(int d, const std::vector<int>& dims, int B) {
-    Slots s;
-    const float delta = 6.0f / B;
-    for (int nd : dims) {
-        float row[2][8] = {};
-        for (int a = 0; a < nd; ++a) {
-            float norm = 0.0f;
-            for (int j = 0; j < d; ++j) {
-                row[a][j] = urand() - 0.5f;
-                norm += row[a][j] * row[a][j];
-            }
-            for (int j = 0; j < d; ++j) row[a][j] /= std::sqrt(norm);
-        }
-        for (int a = 0; a < 2; ++a)
-            for (int j = 0; j < 8; ++j) s.desc.push_back(row[a][j]);
-        for (int a = 0; a < 2; ++a) {
-            s.desc.push_back(-3.0f + 0.5f * delta);
-            s.desc.push_back(3.0f - 0.5f * delta);
-            s.desc.push_back(1.0f / delta);
-        }
-        s.desc.push_back(0.0f);
-        s.desc.push_back(0.0f);
-        const int size = nd == 1 ? B : B * B;
-        s.meta.push_back(nd);
-        s.meta.push_back(B);
-        s.meta.push_back(nd == 1 ? 1 : B);
-        s.meta.push_back((int32_t)s.tables.size());
-        for (int i = 0; i < size; ++i) s.tables.push_back(urand() < 0.15f ? 0.0f : 2.0f * urand());
-        ++s.n;
-    }
-    if (s.tables.empty()) s.tables.push_back(0.0f);
-    return s;
-}
+// Metropolis-Hastings section of the sanitizer driver (mentflow_amd/csrc/mcmc.hip).  tests/emu/build_sanitize.sh links it into
+// tests/emu/sanitize_emu (AddressSanitizer + UndefinedBehaviorSanitizer, the fiber emulator's exactly-sized, guard-paged
+// dynamic LDS), whose main, in sanitize_main.cpp, calls sanitize_mcmc().  It calls mf_mcmc_ment_steps on small synthetic inputs
+// whose buffers have exactly the documented sizes: tables in LDS and beyond it, d = 1 and d = 8, zero slots, a chain count that
+// is not a multiple of the workgroup, out == NULL, a keep_every that never hits, runs cut into launches, NaN noise, and the
+// refusals.  Any out-of-range index or undefined arithmetic aborts.
+#include "sanitize_common.h"
 
 struct Run {
     std::vector<float> x, noise, scale, out;
@@ -139,7 +67,8 @@ static void steps_on(const Slots& s, int d, int kind) {
     for (float v : n.x) check(std::isfinite(v), "finite states");
 }
 
-int main() {
+void sanitize_mcmc() {
+    seed(777u);
     for (int d : {1, 3, 8}) {
         std::vector<int> small = d == 1 ? std::vector<int>{1, 1, 1} : std::vector<int>{1, 2, 1, 1, 2};
         steps_on(make_slots(d, small, 12), d, 1);              // tables in LDS, Gaussian prior
@@ -162,5 +91,4 @@ int main() {
                              4, 0, r.scale.data(), 0, (int64_t)1 << 50, r.out.data(), r.accepted.data(), nullptr) != 0,
           "keep_every beyond 2^40 refused");
     printf("SANITIZE MCMC OK\n");
-    return 0;
 }

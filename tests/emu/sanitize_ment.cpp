@@ -1,77 +1,11 @@
 // TEST INFRASTRUCTURE — NOT PRODUCT CODE.
-// Sanitizer driver for the classical-MENT entry points (mentflow_amd/csrc/ment.hip): built by tests/test_ment_sanitize.py
-// with the flags of tests/emu/build_sanitize.sh (AddressSanitizer + UndefinedBehaviorSanitizer, the fiber emulator's
-// exactly-sized, guard-paged dynamic LDS), it calls every mf_ment_* entry point on small synthetic inputs: tables in LDS and
-// beyond it, multiply mode, NaN rows, every prior kind, grids with a tail block, sampling over several blocks with and
-// without noise, and integrals of more than one 4096-point chunk.  Any out-of-range index or undefined arithmetic aborts.
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-
-#include "../../include/mentflow_hip.h"
-
-static unsigned g_seed = 4242u;
-static float urand() {                         // [0, 1)
-    g_seed = g_seed * 1664525u + 1013904223u;
-    return (float)(g_seed >> 8) / 16777216.0f;
-}
-#define CK(call)                                                                 \
-    do {                                                                         \
-        if ((call) != 0) {                                                       \
-            fprintf(stderr, "FAILED %s: %s\n", #call, mf_last_error());          \
-            exit(2);                                                             \
-        }                                                                        \
-    } while (0)
-
-static void check(bool ok, const char* what) {
-    if (!ok) {
-        fprintf(stderr, "check failed: %s\n", what);
-        exit(3);
-    }
-}
-
-struct Slots {
-    std::vector<float> desc;
-    std::vector<int32_t> meta;
-    std::vector<float> tables;
-    int n = 0;
-};
-
-// `dims[k]` = 1 or 2 axes, B bins per axis on [-3, 3]: descriptor layout of include/mentflow_hip.h
-static Slots make_slots(int d, const std::vector<int>& dims, int B) {
-    Slots s;
-    const float delta = 6.0f / B;
-    for (int nd : dims) {
-        float row[2][8] = {};
-        for (int a = 0; a < nd; ++a) {
-            float norm = 0.0f;
-            for (int j = 0; j < d; ++j) {
-                row[a][j] = urand() - 0.5f;
-                norm += row[a][j] * row[a][j];
-            }
-            for (int j = 0; j < d; ++j) row[a][j] /= std::sqrt(norm);
-        }
-        for (int a = 0; a < 2; ++a)
-            for (int j = 0; j < 8; ++j) s.desc.push_back(row[a][j]);
-        for (int a = 0; a < 2; ++a) {
-            s.desc.push_back(-3.0f + 0.5f * delta);
-            s.desc.push_back(3.0f - 0.5f * delta);
-            s.desc.push_back(1.0f / delta);
-        }
-        s.desc.push_back(0.0f);
-        s.desc.push_back(0.0f);
-        const int size = nd == 1 ? B : B * B;
-        s.meta.push_back(nd);
-        s.meta.push_back(B);
-        s.meta.push_back(nd == 1 ? 1 : B);
-        s.meta.push_back((int32_t)s.tables.size());
-        for (int i = 0; i < size; ++i) s.tables.push_back(urand() < 0.15f ? 0.0f : 2.0f * urand());
-        ++s.n;
-    }
-    if (s.tables.empty()) s.tables.push_back(0.0f);
-    return s;
-}
+// Classical-MENT section of the sanitizer driver (mentflow_amd/csrc/ment.hip).  tests/emu/build_sanitize.sh links it into
+// tests/emu/sanitize_emu (AddressSanitizer + UndefinedBehaviorSanitizer, the fiber emulator's exactly-sized, guard-paged
+// dynamic LDS), whose main, in sanitize_main.cpp, calls sanitize_ment().  It calls every mf_ment_* entry point on small synthetic
+// inputs: tables in LDS and beyond it, multiply mode, NaN rows, every prior kind, grids with a tail block, sampling over several
+// blocks with and without noise, and integrals of more than one 4096-point chunk.  Any out-of-range index or undefined
+// arithmetic aborts.
+#include "sanitize_common.h"
 
 static std::vector<float> points(int64_t n, int d) {
     std::vector<float> x((size_t)n * d);
@@ -202,10 +136,10 @@ static void integrate() {
     }
 }
 
-int main() {
+void sanitize_ment() {
+    seed(4242u);
     prob_points();
     grid_and_sample();
     integrate();
     printf("SANITIZE MENT OK\n");
-    return 0;
 }
