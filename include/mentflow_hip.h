@@ -209,6 +209,24 @@ int mf_proj_kde2d_bwd(const float* x, int64_t n, int d, const float* V0, const f
                       const float* coords_x, int Bx, float sigma_x, int radius_x, const float* coords_y, int By,
                       float sigma_y, int radius_y, const float* gS, float* gx, int accumulate, void* stream);
 
+/* The launch shape one of the four entry points above takes for a call of these sizes in THIS process (the MENTFLOW_KDE*
+ * tuning variables, read once, included): `kernel` 0 = mf_proj_kde1d_fwd, 1 = mf_proj_kde1d_bwd, 2 = mf_proj_kde2d_fwd,
+ * 3 = mf_proj_kde2d_bwd; 1-D: Bx = bins, radius_x = radius, By and radius_y are ignored.  Fills out[MF_KDE_PLAN_FIELDS]
+ * (a HOST array).  Returns 1, with the reason in mf_last_error(), where the entry point would refuse the sizes or a tuning
+ * variable.  Pure host arithmetic: no HIP call, nothing enqueued.  Tests pin the launch path of each case with it and
+ * tools/kde_sweep.py records the shape it timed.  A purely additive entry point: MF_ABI_VERSION stays 5.                */
+#define MF_KDE_PLAN_WINDOW 0    /* kernel instance: 4 = factorised radius-4 window, 0 = run-time radius                  */
+#define MF_KDE_PLAN_BLOCK 1     /* threads per workgroup: 256, 512 or 1024                                               */
+#define MF_KDE_PLAN_PG 2        /* projections whose images one workgroup holds in LDS                                   */
+#define MF_KDE_PLAN_GROUPS 3    /* ceil(P / PG): grid.y of a forward, passes of a backward                               */
+#define MF_KDE_PLAN_PER_WG 4    /* particles per workgroup                                                               */
+#define MF_KDE_PLAN_SPLIT 5     /* 1-D backward: lanes per particle (CH); 2-D backward: particles per thread (NPT); else 0 */
+#define MF_KDE_PLAN_GRID_X 6    /* workgroups along the particles                                                        */
+#define MF_KDE_PLAN_LDS_BYTES 7 /* dynamic LDS of a workgroup                                                            */
+#define MF_KDE_PLAN_SHIFT 8     /* forwards: s of the 2^(s-50) accumulator units above; backwards: 0                     */
+#define MF_KDE_PLAN_FIELDS 9
+int mf_proj_kde_plan(int kernel, int64_t n, int P, int Bx, int By, int radius_x, int radius_y, int64_t* out);
+
 /* Thin multipole kick ahead of a linear map (the non-linear transport of experiments/rec_2d/nonlinear:
  * mentflow/simulate/transform.py:78-146, orders 3..5, k = strength / (order-1)!): u = kick(x), and its adjoint.   */
 int mf_multipole_kick_fwd(const float* x, int64_t n, int d, int order, float k, int skew, float* u, void* stream);

@@ -72,6 +72,7 @@ PROTOTYPES = {
                                  _ptr, _ptr, _ptr]),
     "mf_proj_kde2d_bwd": (_i32, [_ptr, _i64, _i32, _ptr, _ptr, _i32, _ptr, _i32, _f32, _i32, _ptr, _i32, _f32, _i32,
                                  _ptr, _ptr, _i32, _ptr]),
+    "mf_proj_kde_plan": (_i32, [_i32, _i64, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_int64)]),
     "mf_multipole_kick_fwd": (_i32, [_ptr, _i64, _i32, _i32, _f32, _i32, _ptr, _ptr]),
     "mf_multipole_kick_bwd": (_i32, [_ptr, _i64, _i32, _i32, _f32, _i32, _ptr, _ptr, _ptr]),
     "mf_proj_hist1d_counts": (_i32, [_ptr, _i64, _i32, _ptr, _i32, _ptr, _i32, _ptr, _ptr]),

@@ -23,14 +23,16 @@
 // row, private copies per lane: all within 10 %; 2.6-2.75 with only 4 waves per CU) — the float LDS atomic is 10x slower,
 // and bank conflicts do not matter: the atomic unit is the bottleneck either way, so the image is kept once (an earlier
 // version replicated it per lane group; that bought nothing and was removed), occupancy is what counts.
+#include <type_traits>
+
 #include "common.h"
+#include "kde_plan.h"
 
 namespace mf {
 
 constexpr int KDE_DMAX = 8;          // phase-space dimension limit of the projection kernels
 constexpr int KDE_BLOCK = 256;
 constexpr int KDE_LDS_FLOATS = 24576;   // 96 KiB histogram image per workgroup
-constexpr int KDE_RMAX2D = 5;
 
 __device__ __forceinline__ void load_row(const float* __restrict__ x, int64_t p, int d, float (&xv)[KDE_DMAX]) {
 #pragma unroll
@@ -56,9 +58,7 @@ __device__ __forceinline__ int centre_bin(float u, float c0, float inv_delta, in
 typedef unsigned long long u64;
 constexpr double KDE_FIX_INV = 1.0 / 1125899906842624.0; // 2^-50: fixed-point quantum of the LDS histogram image
 constexpr float KDE_FIX_MIN = 8.8817841970012523e-16f;   // 2^-50: smaller weights round down to zero
-constexpr int KDE_MAX_PER_WG = 8192;                     // particles per workgroup: 2^13 * 2^50 < 2^64, no overflow
 constexpr float KDE_EXP2_SCALE = 0.7213475204444817f;    // log2(e) / 2:  exp(-r^2/2) = exp2(-KDE_EXP2_SCALE r^2)
-constexpr int KDE_VS = 8;                                // LDS row stride of the projection vectors (two 16-byte reads)
 
 __device__ __forceinline__ float gauss_weight(float r) { return __builtin_amdgcn_exp2f(-KDE_EXP2_SCALE * r * r); }
 
@@ -79,11 +79,6 @@ __device__ __forceinline__ u64 to_fix(float w) {
 __device__ __forceinline__ void fix_flush(u64* __restrict__ acc, u64 v, int shift) {
     v >>= shift;
     if (v != 0) atomicAdd(acc, v);
-}
-static int kde_global_shift(int64_t n) {
-    int k = 0;
-    while (((int64_t)1 << k) < n) ++k;
-    return k > 13 ? k - 13 : 0;
 }
 
 // Gaussian window, partly factorised.  With kc the centre bin of u, r0 = (u - c_kc) / sigma and s = delta / sigma, bin
@@ -875,226 +870,114 @@ static int fix_finish(const u64* Sacc, float* S, int64_t total, int shift, void*
     return check_launch("acc_to_float");
 }
 
-static int env_int(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
+// The launch shape of the four launchers below is decided in kde_plan.h, with the tuning variables as read once per process.
+static_assert(KDE_CUS == NUM_CU, "kde_plan.h plans for the chip of common.h");
+static int process_plan(int kernel, int64_t n, int P, int Bx, int By, int radius_x, int radius_y, KdePlan& p) {
+    static const KdeKnobs knobs = kde_knobs_from_env();
+    return kde_plan(kernel, n, P, Bx, By, radius_x, radius_y, knobs, p) ? 0 : fail("%s", p.err);
+}
+static int launch_plan(int kernel, int64_t n, int d, int P, int Bx, int By, int radius_x, int radius_y, KdePlan& p) {
+    if (d < 1 || d > KDE_DMAX) return fail("projection kernels support 1 <= d <= %d (got d=%d)", KDE_DMAX, d);
+    return process_plan(kernel, n, P, Bx, By, radius_x, radius_y, p);
 }
 
-constexpr size_t KDE_LDS_BYTES = 156 * 1024;          // dynamic LDS a workgroup may ask for (of 160 KiB)
+extern "C" int mf_proj_kde_plan(int kernel, int64_t n, int P, int Bx, int By, int radius_x, int radius_y, int64_t* out) {
+    KdePlan p;
+    if (process_plan(kernel, n, P, Bx, By, radius_x, radius_y, p)) return 1;
+    const int64_t fields[MF_KDE_PLAN_FIELDS] = {p.window, p.block,  p.Pg, p.groups, p.per_wg,        // in the order of MF_KDE_PLAN_*
+                                                p.split,  p.grid_x, (int64_t)p.smem, p.shift};
+    memcpy(out, fields, sizeof(fields));
+    return 0;
+}
 
-// particles per forward workgroup: enough workgroups to cover the chip `waves` times over, a multiple of the block
-// size, at most KDE_MAX_PER_WG (fixed-point headroom)
-static int kde_per_wg(int64_t n, int ngroups, int block, int waves) {
-    int64_t want = (n * ngroups + (int64_t)waves * NUM_CU - 1) / ((int64_t)waves * NUM_CU);
-    want = ((want + block - 1) / block) * block;
-    if (want < block) want = block;
-    if (want > KDE_MAX_PER_WG) want = (KDE_MAX_PER_WG / block) * block;
-    return (int)want;
+// f(std::integral_constant<int, V>) for the V of the list that v equals.  kde_plan returns no other value: the last one is not tested.
+template <int V, int... Rest, class F>
+static void pick(int v, F&& f) {
+    if constexpr (sizeof...(Rest) > 0) {
+        if (v != V) return pick<Rest...>(v, f);
+    }
+    f(std::integral_constant<int, V>{});
+}
+// the built instances: window {4, 0} x block {256, 512, 1024} (2-D backward: x particles per thread {1, 2, 4})
+template <class F>
+static void pick_window_block(const KdePlan& p, F&& f) {
+    pick<4, 0>(p.window, [&](auto RT) { pick<256, 512, 1024>(p.block, [&](auto BL) { f(RT, BL); }); });
 }
 
 extern "C" int mf_proj_kde1d_fwd(const float* x, int64_t n, int d, const float* V, int P, const float* coords, int B,
                                   float sigma, int radius, float* S, void* ws, void* stream) {
-    if (kde_check(n, d, P, B)) return 1;
+    KdePlan p;
+    if (launch_plan(KDE1D_FWD, n, d, P, B, 1, radius, radius, p)) return 1;
     u64* Sfix = reinterpret_cast<u64*>(ws);
     if (hipMemsetAsync(Sfix, 0, sizeof(u64) * (size_t)P * B, (hipStream_t)stream) != hipSuccess) return fail("memset ws");
     if (n > 0) {
-        const int R = radius < 0 ? 0 : (radius > B ? B : radius);
-        const size_t per_proj = sizeof(u64) * (size_t)B + sizeof(float) * KDE_VS;
-        if (per_proj + sizeof(float) * B > KDE_LDS_BYTES) return fail("too many bins for the LDS image (%d)", B);
-        // Large batches: all projections that fit one image (C4: 100 x 64 bins = 51 KiB), big workgroups.  Small batches
-        // (the reference's 25 000 particles): 256 threads and many small projection groups so that ~4 * NUM_CU
-        // workgroups exist.
-        const bool small = n <= 65536;
-        // tuned on MI355X at C4 (tools/kde_sweep.py, profiles/r02_kde_sweep_1d.txt): 1024 threads, ~52 KiB images (two
-        // workgroups = 32 waves per CU): 1.11-1.13 ms against 1.19-1.51 ms for 256 threads; 4 workgroup waves over the
-        // chip (4096 particles per workgroup at C4) rather than 8: 2 % slower, half the flush atomics
-        static const int block_env = env_int("MENTFLOW_KDE1D_BLOCK", 0), waves_env = env_int("MENTFLOW_KDE1D_WAVES", 4);
-        static const int lds_env = env_int("MENTFLOW_KDE1D_LDS", 0);
-        const int block = block_env ? block_env : (small ? 256 : 1024);
-        size_t budget = lds_env ? (size_t)lds_env : (size_t)52 * 1024;
-        if (budget > KDE_LDS_BYTES) budget = KDE_LDS_BYTES;
-        int Pg = (int)((budget - sizeof(float) * B) / per_proj);
-        if (Pg < 1) Pg = 1;
-        if (Pg > P) Pg = P;
-        if (small) {
-            const int64_t wg_particles = (n + block - 1) / block;
-            const int64_t want_groups = (4 * NUM_CU + wg_particles - 1) / wg_particles;
-            if (want_groups > 1) {
-                int pg_small = (int)((P + want_groups - 1) / want_groups);
-                if (pg_small < 4) pg_small = P < 4 ? P : 4;
-                if (pg_small < Pg) Pg = pg_small;
-            }
-        } else {
-            const int ng = (P + Pg - 1) / Pg;                 // equal-sized groups
-            Pg = (P + ng - 1) / ng;
-        }
-        const int ngroups = (P + Pg - 1) / Pg;
-        const size_t smem = per_proj * Pg + sizeof(float) * B;
-        const int per_wg = small ? block : kde_per_wg(n, ngroups, block, waves_env);
-        const int64_t G = (n + per_wg - 1) / per_wg;
         ProfScope prof(PK_KDE1D_FWD, stream);
-        bool launched = false;
-#define KDE1D_CASE(RTV, BL)                                                                                           \
-    if (!launched && (R == 4) == (RTV == 4) && block == BL) {                                                         \
-        MF_ALLOW_DYN_SMEM((proj_kde1d_fwd_kernel<RTV, BL>), smem);                                                    \
-        MF_LAUNCH((proj_kde1d_fwd_kernel<RTV, BL>), dim3((unsigned)G, ngroups), BL, smem, stream, x, n, d, V, P, Pg,   \
-                  coords, B, 1.0f / sigma, R, Sfix, per_wg, kde_global_shift(n));                                                          \
-        launched = true;                                                                                              \
-    }
-        KDE1D_CASE(4, 256) KDE1D_CASE(0, 256) KDE1D_CASE(4, 512) KDE1D_CASE(0, 512) KDE1D_CASE(4, 1024) KDE1D_CASE(0, 1024)
-#undef KDE1D_CASE
-        if (!launched) return fail("no 1-D KDE forward instance for block=%d (256, 512, 1024)", block);
+        pick_window_block(p, [&](auto RT, auto BL) {
+            MF_ALLOW_DYN_SMEM((proj_kde1d_fwd_kernel<RT, BL>), p.smem);
+            MF_LAUNCH((proj_kde1d_fwd_kernel<RT, BL>), dim3((unsigned)p.grid_x, p.groups), BL, p.smem, stream, x, n, d, V, P, p.Pg,
+                      coords, B, 1.0f / sigma, kde_radius_1d(radius, B), Sfix, p.per_wg, p.shift);
+        });
         if (check_launch("mf_proj_kde1d_fwd")) return 1;
     }
-    return fix_finish(Sfix, S, (int64_t)P * B, kde_global_shift(n), stream);
+    return fix_finish(Sfix, S, (int64_t)P * B, p.shift, stream);
 }
 
 extern "C" int mf_proj_kde1d_bwd(const float* x, int64_t n, int d, const float* V, int P, const float* coords, int B,
                                   float sigma, int radius, const float* gS, float* gx, int accumulate, void* stream) {
-    if (kde_check(n, d, P, B)) return 1;
-    const size_t per_proj = sizeof(float) * ((size_t)B + KDE_VS);
-    if (per_proj + sizeof(float) * B > KDE_LDS_BYTES) return fail("too many bins for the LDS image (%d)", B);
+    KdePlan p;
+    if (launch_plan(KDE1D_BWD, n, d, P, B, 1, radius, radius, p)) return 1;
     if (n == 0) return 0;
-    const int R = radius < 0 ? 0 : (radius > B ? B : radius);
-    static const int block_env = env_int("MENTFLOW_KDE1D_BWD_BLOCK", 0), lds_env = env_int("MENTFLOW_KDE1D_BWD_LDS", 0);
-    const int block = block_env ? block_env : (n >= 262144 ? 512 : 256);
-    size_t budget = lds_env ? (size_t)lds_env : (size_t)52 * 1024;
-    if (budget > KDE_LDS_BYTES) budget = KDE_LDS_BYTES;
-    int Pg = (int)((budget - sizeof(float) * B) / per_proj);
-    if (Pg < 1) Pg = 1;
-    if (Pg > P) Pg = P;
-    const size_t smem = per_proj * Pg + sizeof(float) * B;
-    // lanes per particle: enough workgroups to give every SIMD a wave (>= 1024 workgroups of 4 waves), at most 8
-    int CH = 1;
-    while (CH < 8 && CH * 2 <= P && (n * CH + block - 1) / block < 4 * NUM_CU) CH *= 2;
-    const int64_t G = (n * CH + block - 1) / block;
     ProfScope prof(PK_KDE1D_BWD, stream);
-    bool launched = false;
-#define KDE1DB_CASE(RTV, BL)                                                                                          \
-    if (!launched && (R == 4) == (RTV == 4) && block == BL) {                                                         \
-        MF_ALLOW_DYN_SMEM((proj_kde1d_bwd_kernel<RTV, BL>), smem);                                                    \
-        MF_LAUNCH((proj_kde1d_bwd_kernel<RTV, BL>), dim3((unsigned)G), BL, smem, stream, x, n, d, V, P, Pg, coords, B,  \
-                  1.0f / sigma, R, gS, gx, accumulate, CH);                                                           \
-        launched = true;                                                                                              \
-    }
-    KDE1DB_CASE(4, 256) KDE1DB_CASE(0, 256) KDE1DB_CASE(4, 512) KDE1DB_CASE(0, 512) KDE1DB_CASE(4, 1024) KDE1DB_CASE(0, 1024)
-#undef KDE1DB_CASE
-    if (!launched) return fail("no 1-D KDE backward instance for block=%d (256, 512, 1024)", block);
+    pick_window_block(p, [&](auto RT, auto BL) {
+        MF_ALLOW_DYN_SMEM((proj_kde1d_bwd_kernel<RT, BL>), p.smem);
+        MF_LAUNCH((proj_kde1d_bwd_kernel<RT, BL>), dim3((unsigned)p.grid_x), BL, p.smem, stream, x, n, d, V, P, p.Pg, coords, B,
+                  1.0f / sigma, kde_radius_1d(radius, B), gS, gx, accumulate, p.split);
+    });
     return check_launch("mf_proj_kde1d_bwd");
-}
-
-static int kde2d_check(int d, int P, int Bx, int By, int rx, int ry, size_t entry_bytes) {
-    if (rx > KDE_RMAX2D || ry > KDE_RMAX2D)
-        return fail("2-D KDE kernel supports a truncation radius <= %d bins (bandwidth <= 0.6 bin widths)", KDE_RMAX2D);
-    if (entry_bytes * (size_t)Bx * By + sizeof(float) * (2 * KDE_VS + Bx + By) > KDE_LDS_BYTES)
-        return fail("2-D histogram image %dx%d exceeds the LDS budget", Bx, By);
-    return 0;
 }
 
 extern "C" int mf_proj_kde2d_fwd(const float* x, int64_t n, int d, const float* V0, const float* V1, int P,
                                   const float* coords_x, int Bx, float sigma_x, int radius_x, const float* coords_y,
                                   int By, float sigma_y, int radius_y, float* S, void* ws, void* stream) {
-    if (kde_check(n, d, P, Bx) || kde_check(n, d, P, By)) return 1;
-    if (kde2d_check(d, P, Bx, By, radius_x, radius_y, sizeof(u64))) return 1;
-    const int BB = Bx * By;
+    KdePlan p;
+    if (launch_plan(KDE2D_FWD, n, d, P, Bx, By, radius_x, radius_y, p)) return 1;
     u64* Sfix = reinterpret_cast<u64*>(ws);
-    if (hipMemsetAsync(Sfix, 0, sizeof(u64) * (size_t)P * BB, (hipStream_t)stream) != hipSuccess) return fail("memset ws");
+    if (hipMemsetAsync(Sfix, 0, sizeof(u64) * (size_t)P * Bx * By, (hipStream_t)stream) != hipSuccess) return fail("memset ws");
     if (n > 0) {
-        // tuned on MI355X at C5 (tools/kde_sweep.py): one 85 x 85 image (58 KiB) per 1024-thread workgroup, two
-        // workgroups per CU: 6.0 ms against 6.7 (512 threads) / 9-16 ms (256 threads, the r01 shape)
-        static const int lds_env = env_int("MENTFLOW_KDE2D_FWD_LDS", 60 * 1024), block_env = env_int("MENTFLOW_KDE2D_BLOCK", 1024);
-        static const int waves_env = env_int("MENTFLOW_KDE2D_WAVES", 4);
-        const size_t per_proj = sizeof(u64) * (size_t)BB + sizeof(float) * 2 * KDE_VS;
-        const size_t fixed = sizeof(float) * ((size_t)Bx + By);
-        size_t budget = (size_t)lds_env;
-        if (budget > KDE_LDS_BYTES) budget = KDE_LDS_BYTES;
-        if (budget < per_proj + fixed) budget = per_proj + fixed;
-        int Pg = (int)((budget - fixed) / per_proj);
-        if (Pg > P) Pg = P;
-        const int block = block_env;
-        const size_t smem = per_proj * Pg + fixed;
-        const int ngroups = (P + Pg - 1) / Pg;
-        const int per_wg = kde_per_wg(n, ngroups, block, waves_env);
-        const int64_t G = (n + per_wg - 1) / per_wg;
-        const int RT = (radius_x == 4 && radius_y == 4) ? 4 : 0;
         ProfScope prof(PK_KDE2D_FWD, stream);
-        bool launched = false;
-#define KDE2D_CASE(RTV, BL)                                                                                           \
-    if (!launched && RT == RTV && block == BL) {                                                                      \
-        MF_ALLOW_DYN_SMEM((proj_kde2d_fwd_kernel<RTV, BL>), smem);                                                    \
-        MF_LAUNCH((proj_kde2d_fwd_kernel<RTV, BL>), dim3((unsigned)G, ngroups), BL, smem, stream, x, n, d, V0, V1, P,  \
-                  Pg, coords_x, Bx, 1.0f / sigma_x, radius_x, coords_y, By, 1.0f / sigma_y, radius_y, Sfix, per_wg,        \
-                  kde_global_shift(n));   \
-        launched = true;                                                                                              \
-    }
-        KDE2D_CASE(4, 256) KDE2D_CASE(0, 256) KDE2D_CASE(4, 512) KDE2D_CASE(0, 512) KDE2D_CASE(4, 1024) KDE2D_CASE(0, 1024)
-#undef KDE2D_CASE
-        if (!launched) return fail("no 2-D KDE forward instance for block=%d (256, 512, 1024)", block);
+        pick_window_block(p, [&](auto RT, auto BL) {
+            MF_ALLOW_DYN_SMEM((proj_kde2d_fwd_kernel<RT, BL>), p.smem);
+            MF_LAUNCH((proj_kde2d_fwd_kernel<RT, BL>), dim3((unsigned)p.grid_x, p.groups), BL, p.smem, stream, x, n, d, V0, V1, P,
+                      p.Pg, coords_x, Bx, 1.0f / sigma_x, radius_x, coords_y, By, 1.0f / sigma_y, radius_y, Sfix, p.per_wg, p.shift);
+        });
         if (check_launch("mf_proj_kde2d_fwd")) return 1;
     }
-    return fix_finish(Sfix, S, (int64_t)P * BB, kde_global_shift(n), stream);
+    return fix_finish(Sfix, S, (int64_t)P * Bx * By, p.shift, stream);
 }
 
 extern "C" int mf_proj_kde2d_bwd(const float* x, int64_t n, int d, const float* V0, const float* V1, int P,
                                   const float* coords_x, int Bx, float sigma_x, int radius_x, const float* coords_y,
                                   int By, float sigma_y, int radius_y, const float* gS, float* gx, int accumulate,
                                   void* stream) {
-    if (kde_check(n, d, P, Bx) || kde_check(n, d, P, By)) return 1;
-    if (kde2d_check(d, P, Bx, By, radius_x, radius_y, sizeof(float))) return 1;
+    KdePlan p;
+    if (launch_plan(KDE2D_BWD, n, d, P, Bx, By, radius_x, radius_y, p)) return 1;
     if (n == 0) return 0;
-    const int BB = Bx * By;
-    // tuned on MI355X at C5 (tools/kde_sweep.py): 1024 threads x 4 particles each with four 85 x 85 images (116 KiB)
-    // staged per pass — 3.8 ms against 5.3 ms for the r01 shape (256 threads x 4, one image); staging an image costs
-    // L2 -> LDS traffic per workgroup, so fat workgroups win once there are enough particles to fill the chip with them.
-    // Smaller batches step down to (1024, 2), (1024, 1), (512, 1), (256, 1) until >= 2 workgroups per CU exist.
-    static const int lds_env = env_int("MENTFLOW_KDE2D_BWD_LDS", 0), block_env = env_int("MENTFLOW_KDE2D_BWD_BLOCK", 0);
-    static const int npt_env = env_int("MENTFLOW_KDE2D_BWD_NPT", 0);
-    int block_h = 256, npt_h = 1;
-    {
-        static const int shapes[5][2] = {{1024, 4}, {1024, 2}, {1024, 1}, {512, 1}, {256, 1}};
-        for (int k = 0; k < 5; ++k) {
-            block_h = shapes[k][0];
-            npt_h = shapes[k][1];
-            if (n / ((int64_t)block_h * npt_h) >= 2 * NUM_CU) break;
-        }
-    }
-    const size_t per_proj = sizeof(float) * ((size_t)BB + 2 * KDE_VS);
-    const size_t fixed = sizeof(float) * ((size_t)Bx + By);
-    const int block = block_env ? block_env : block_h, npt = npt_env ? npt_env : npt_h;
-    size_t budget = lds_env ? (size_t)lds_env : (block >= 1024 ? (size_t)118 * 1024 : (block >= 512 ? (size_t)59 * 1024 : (size_t)30 * 1024));
-    if (budget > KDE_LDS_BYTES) budget = KDE_LDS_BYTES;
-    if (budget < per_proj + fixed) budget = per_proj + fixed;
-    int Pg = (int)((budget - fixed) / per_proj);
-    if (Pg > P) Pg = P;
-    const size_t smem = per_proj * Pg + fixed;
-    const int64_t per_wg = (int64_t)block * npt;
-    const int64_t G = (n + per_wg - 1) / per_wg;
-    const int RT = (radius_x == 4 && radius_y == 4) ? 4 : 0;
     ProfScope prof(PK_KDE2D_BWD, stream);
-    bool launched = false;
-#define KDE2DB_CASE(RTV, BL, NP)                                                                                      \
-    if (!launched && RT == RTV && block == BL && npt == NP) {                                                         \
-        MF_ALLOW_DYN_SMEM((proj_kde2d_bwd_kernel<RTV, BL, NP>), smem);                                                \
-        MF_LAUNCH((proj_kde2d_bwd_kernel<RTV, BL, NP>), dim3((unsigned)G), BL, smem, stream, x, n, d, V0, V1, P, Pg,   \
-                  coords_x, Bx, 1.0f / sigma_x, radius_x, coords_y, By, 1.0f / sigma_y, radius_y, gS, gx, accumulate); \
-        launched = true;                                                                                              \
-    }
-#define KDE2DB_CASES(BL, NP) KDE2DB_CASE(4, BL, NP) KDE2DB_CASE(0, BL, NP)
-    KDE2DB_CASES(256, 1) KDE2DB_CASES(256, 2) KDE2DB_CASES(256, 4) KDE2DB_CASES(512, 1) KDE2DB_CASES(512, 2) KDE2DB_CASES(512, 4)
-    KDE2DB_CASES(1024, 1) KDE2DB_CASES(1024, 2) KDE2DB_CASES(1024, 4)
-#undef KDE2DB_CASES
-#undef KDE2DB_CASE
-    if (!launched) return fail("no 2-D KDE backward instance for block=%d npt=%d", block, npt);
+    pick_window_block(p, [&](auto RT, auto BL) {
+        pick<1, 2, 4>(p.split, [&](auto NP) {
+            MF_ALLOW_DYN_SMEM((proj_kde2d_bwd_kernel<RT, BL, NP>), p.smem);
+            MF_LAUNCH((proj_kde2d_bwd_kernel<RT, BL, NP>), dim3((unsigned)p.grid_x), BL, p.smem, stream, x, n, d, V0, V1, P, p.Pg,
+                      coords_x, Bx, 1.0f / sigma_x, radius_x, coords_y, By, 1.0f / sigma_y, radius_y, gS, gx, accumulate);
+        });
+    });
     return check_launch("mf_proj_kde2d_bwd");
 }
 
 // geometry of the hard-binned 2-D counts kernel: as many int images as fit the budget
-static int kde2d_geometry(int d, int P, int Bx, int By, int rx, int ry, int* Pg, size_t* smem, int extra,
-                          int budget_floats = KDE_LDS_FLOATS) {
-    (void)rx; (void)ry;
+static int kde2d_geometry(int d, int P, int Bx, int By, int* Pg, size_t* smem, int extra) {
     const int BB = Bx * By;
     if (BB > KDE_LDS_FLOATS) return fail("2-D histogram image %dx%d exceeds the LDS budget", Bx, By);
-    int g = budget_floats / BB;
+    int g = KDE_LDS_FLOATS / BB;
     if (g < 1) g = 1;
     if (g > P) g = P;
     *Pg = g;
@@ -1123,7 +1006,7 @@ extern "C" int mf_proj_hist2d_counts(const float* x, int64_t n, int d, const flo
     if (kde_check(n, d, P, Bx) || kde_check(n, d, P, By)) return 1;
     int Pg;
     size_t smem;
-    if (kde2d_geometry(d, P, Bx, By, 0, 0, &Pg, &smem, 2)) return 1;
+    if (kde2d_geometry(d, P, Bx, By, &Pg, &smem, 2)) return 1;
     if (hipMemsetAsync(counts, 0, sizeof(int32_t) * (size_t)P * Bx * By, (hipStream_t)stream) != hipSuccess) return fail("memset");
     if (n == 0) return 0;
     const int ngroups = (P + Pg - 1) / Pg;

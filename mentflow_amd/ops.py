@@ -360,6 +360,17 @@ class ProjKde2dFn(torch.autograd.Function):
         return gx, None, None, None, None, None, None, None, None
 
 
+KDE_PLAN_KERNELS = ("kde1d_fwd", "kde1d_bwd", "kde2d_fwd", "kde2d_bwd")
+KDE_PLAN_FIELDS = ("window", "block", "Pg", "groups", "per_wg", "split", "grid_x", "lds_bytes", "shift")   # MF_KDE_PLAN_*
+
+
+def kde_plan(kernel: str, n: int, P: int, Bx: int, By: int = 1, radius_x: int = 4, radius_y: int = 4) -> dict:
+    """The launch shape mf_proj_<kernel> takes for these sizes in this process (mf_proj_kde_plan: host arithmetic only)."""
+    out = (C.c_int64 * len(KDE_PLAN_FIELDS))()
+    call("mf_proj_kde_plan", KDE_PLAN_KERNELS.index(kernel), n, P, Bx, By, radius_x, radius_y, out)
+    return dict(zip(KDE_PLAN_FIELDS, out))
+
+
 class MultipoleKickFn(torch.autograd.Function):
     """u = MultipoleTransform(order, strength, skew)(x)  (mentflow/simulate/transform.py:98-143)."""
 

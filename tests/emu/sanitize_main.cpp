@@ -13,6 +13,7 @@
 #include <cstring>
 #include <vector>
 
+#include "../../mentflow_amd/csrc/kde_plan.h"
 #include "sanitize_common.h"
 
 static unsigned g_seed = 12345u;
@@ -209,6 +210,76 @@ static void kde2d(int64_t n, int d, int P, int Bx, int By, float bwx, float bwy,
     printf("  kde2d n=%ld d=%d P=%d %dx%d radii %d,%d\n", (long)n, d, P, Bx, By, rx, ry);
 }
 
+// Launch plans of the four KDE launchers (mentflow_amd/csrc/kde_plan.h: pure host arithmetic): mf_proj_kde_plan for every kernel, then
+// kde_plan itself over the knob grid of tools/kde_sweep.py (both sweeps) and the values a knob must not be allowed to reach a division,
+// an unsigned wrap or a launch with (waves 0, a negative LDS budget, block 300, NPT 3 / -1; an LDS budget of 1 byte is clamped up to
+// one projection), crossed with 1-D and 2-D shapes.  Every accepted plan is launchable; every bad value is refused with a message.
+static void kde_plans() {
+    using namespace mf;
+    for (int kernel = 0; kernel < KDE_KERNELS; ++kernel) {
+        int64_t out[MF_KDE_PLAN_FIELDS];
+        CK(mf_proj_kde_plan(kernel, 70001, 101, 85, kernel >= KDE2D_FWD ? 85 : 1, 4, 4, out));
+        check(out[MF_KDE_PLAN_GRID_X] * out[MF_KDE_PLAN_PER_WG] >= 70001 && out[MF_KDE_PLAN_WINDOW] == 4, "mf_proj_kde_plan");
+        check(mf_proj_kde_plan(kernel, 70001, 0, 85, 85, 4, 4, out) == 1 && mf_last_error()[0] != '\0', "P = 0 is refused");
+    }
+    struct Knob { int kernel, knob, value; };
+    std::vector<std::vector<Knob>> good(1), bad;                                    // good[0]: no knob set
+    for (int b : {256, 512, 1024}) {
+        for (int l : {53000, 79872, 159000})
+            for (int w : {2, 4, 8}) good.push_back({{KDE1D_FWD, KNOB_BLOCK, b}, {KDE1D_FWD, KNOB_LDS, l}, {KDE1D_FWD, KNOB_WAVES, w}});
+        for (int l : {27000, 53000, 98304}) good.push_back({{KDE1D_BWD, KNOB_BLOCK, b}, {KDE1D_BWD, KNOB_LDS, l}});
+        for (int l : {59000, 118000})
+            for (int w : {4, 8, 16}) good.push_back({{KDE2D_FWD, KNOB_BLOCK, b}, {KDE2D_FWD, KNOB_LDS, l}, {KDE2D_FWD, KNOB_WAVES, w}});
+        for (int np : {1, 2, 4})
+            for (int l : {30000, 59000, 118000}) good.push_back({{KDE2D_BWD, KNOB_BLOCK, b}, {KDE2D_BWD, KNOB_NPT, np}, {KDE2D_BWD, KNOB_LDS, l}});
+    }
+    for (int kernel = 0; kernel < KDE_KERNELS; ++kernel) {
+        good.push_back({{kernel, KNOB_LDS, 1}});                                     // clamped up to one projection's image
+        bad.push_back({{kernel, KNOB_LDS, -4096}});
+        bad.push_back({{kernel, KNOB_BLOCK, 300}});
+        if (KDE_KNOB_ENV[kernel][KNOB_WAVES]) bad.push_back({{kernel, KNOB_WAVES, 0}});
+        if (KDE_KNOB_ENV[kernel][KNOB_NPT]) bad.push_back({{kernel, KNOB_NPT, 3}}), bad.push_back({{kernel, KNOB_NPT, -1}});
+    }
+    const int64_t ns[] = {0, 1, 255, 65536, 65537, 262144, (int64_t)1 << 21, (int64_t)1 << 24};
+    const int shapes[][2] = {{2, 1}, {64, 1}, {85, 1}, {4096, 1}, {85, 85}, {16, 11}};   // By = 1: the 1-D kernels
+    long accepted = 0, refused = 0;
+    auto walk = [&](const std::vector<Knob>& cfg, bool is_bad) {
+        KdeKnobs knobs;
+        for (const Knob& k : cfg) knobs.v[k.kernel][k.knob] = k.value;
+        for (int kernel = 0; kernel < KDE_KERNELS; ++kernel)
+            for (int64_t n : ns)
+                for (int P : {1, 3, 101})
+                    for (const auto& sh : shapes)
+                        for (int radius : {4, 5}) {
+                            if ((sh[1] > 1) != (kernel >= KDE2D_FWD)) continue;
+                            KdePlan p;
+                            const bool ok = kde_plan(kernel, n, P, sh[0], sh[1], radius, radius, knobs, p);
+                            if (is_bad && kernel == cfg[0].kernel) {
+                                check(!ok && strstr(p.err, KDE_KNOB_ENV[kernel][cfg[0].knob]) != nullptr, "a bad knob is refused by name");
+                                ++refused;
+                                continue;
+                            }
+                            check(ok, "a plan within the limits is accepted");
+                            ++accepted;
+                            const bool fwd = kernel == KDE1D_FWD || kernel == KDE2D_FWD;
+                            check(p.Pg >= 1 && p.Pg <= P, "1 <= Pg <= P");
+                            check((int64_t)p.groups * p.Pg >= P && P > (int64_t)(p.groups - 1) * p.Pg, "groups cover P without an empty one");
+                            check(p.smem <= KDE_LDS_BYTES, "LDS within the limit");
+                            check(p.block == 256 || p.block == 512 || p.block == 1024, "block has an instance");
+                            check(p.window == 4 || p.window == 0, "window has an instance");
+                            check(p.window == (radius == 4 && sh[0] >= 4 ? 4 : 0), "radius 4 takes the factorised window");
+                            if (kernel == KDE2D_BWD) check(p.split == 1 || p.split == 2 || p.split == 4, "npt has an instance");
+                            if (kernel == KDE1D_BWD) check(p.split >= 1 && p.split <= 8 && p.block % p.split == 0, "CH divides the block");
+                            if (fwd) check(p.per_wg % p.block == 0 && p.per_wg <= KDE_MAX_PER_WG, "forward per_wg: multiple of the block, <= 8192");
+                            check(p.per_wg >= 1 && p.grid_x * p.per_wg >= n && p.grid_x < ((int64_t)1 << 31), "grid covers n");
+                            check(p.shift == (fwd ? kde_global_shift(n) : 0), "shift");
+                        }
+    };
+    for (const auto& cfg : good) walk(cfg, false);
+    for (const auto& cfg : bad) walk(cfg, true);
+    printf("  kde plans: %zu knob settings, %ld plans accepted, %ld refused\n", good.size() + bad.size(), accepted, refused);
+}
+
 static void tail(int64_t n, int d) {
     std::vector<float> x = rnd(n * d, 1.0f), logp = rnd(n, 1.0f), out(2), gx(n * d), coef(1, 0.5f), u(n * d);
     std::vector<double> acc(MF_ENTROPY_SCRATCH_DOUBLES);
@@ -270,6 +341,7 @@ int main(int argc, char** argv) {
     kde2d(700, 6, 3, 20, 24, 0.5f, 0.5f, 4, 4);
     kde2d(400, 4, 2, 85, 85, 0.5f, 0.45f, 4, 4);
     kde2d(300, 2, 2, 17, 13, 0.6f, 0.3f, 5, 3);
+    kde_plans();
     tail(1000, 6);
     tail(333, 2);
     double prof_ms = NAN;                // writes through both pointers (and reports nothing: the emulation records no events)

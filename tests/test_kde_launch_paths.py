@@ -1,22 +1,29 @@
-"""The histogram half of the step, element by element against fp64 on every launch path of mentflow_amd/csrc/kde.hip:
+"""The histogram half of the step, element by element against fp64 on the launch paths of mentflow_amd/csrc/kde.hip:
 projection + KDE forward / backward (1-D and 2-D), the fixed-point accumulation, clipped windows and non-finite rows,
 hard-binned counts, the normalisation + discrepancy tail, the fused loss with MAE / MSE, the entropy sums and the two
 small helpers (mf_scale_rows, mf_gather_f32).  Non-uniform bin edges, which the KDE kernels cannot take, are checked
 through Histogram1D / Histogram2D and MENTFlow.loss (dense evaluation, mentflow_amd/diagnostics/diagnostics.py).
 
 Every reference is plain fp64 torch written from the reference's formulas (histogram.py:11-74, loss.py:7-17,
-entropy.py:58-62).  The parameter ids name the launch each case takes, worked out by `_plan_*` below from the launchers
-of kde.hip: fwd<block>/Pg<projections per group>xG<groups>/w<particles per workgroup>/sh<kde_global_shift>,
+entropy.py:58-62).  Every KDE case carries the launch path it is there for as a literal, which is also its parameter id:
+fwd<block>/Pg<projections per group>xG<groups>/w<particles per workgroup>/sh<kde_global_shift>,
 bwd<block>/ch<lanes per particle> (1-D) or bwd<block>/npt<particles per thread> (2-D), and the window variant
-(fact = factorised radius-4 window, rt<R> = run-time radius R).
+(fact = factorised radius-4 window, rt<R> = run-time radius R).  Before a case runs its kernels it asserts that the
+loaded library plans exactly that path for it (ops.kde_plan -> mf_proj_kde_plan, the host code the launchers themselves
+run: mentflow_amd/csrc/kde_plan.h), and test_case_lists_cover_the_launch_paths states what the lists cover: a threshold
+that moves in kde_plan.h fails one of the two.
 
 Gates (the suite's): histograms rtol 2e-5 + atol 1e-6; particle gradients rtol 1e-3 + atol 2e-5 max|g| + 1e-6; counts
 and a saturated centre bin exact.
 
 The CPU suite runs the emulated build up to 300 000 particles (the emulator takes well under a second per launch
 there); `-m gpu` repeats A-C on the MI355X at 70 001 / 300 000 / 2 097 152 particles (and 16 M for the shift-11
-accumulator), with the fp64 reference computed on the GPU in chunks."""
+accumulator), with the fp64 reference computed on the GPU in chunks.  Only those gpu-marked lists reach forward
+workgroups of more particles than threads (the multi-iteration particle loop: w2048 .. w8192), the 1024-thread 2-D
+backward with 1, 2 and 4 particles per thread, and shift 11; every emulated forward workgroup takes one particle per
+thread."""
 import math
+import re
 
 import numpy as np
 import pytest
@@ -27,71 +34,35 @@ from mentflow_amd import _lib, ops
 from mentflow_amd._lib import call, ptr, stream_ptr
 from oracle import model as om
 
-NUM_CU = 256
 RTOL_S, ATOL_S = 2e-5, 1e-6
 
 
-# ------------------------------------------------------------------------------------------------ launch plans
-# Python restatement of the launch decisions of kde.hip (mf_proj_kde1d_fwd / _bwd, mf_proj_kde2d_fwd / _bwd) with the
-# default tuning knobs: only used to NAME the path of each case.
-def _cdiv(a, b):
-    return -(-a // b)
-
-
-def _shift(n):
-    k = 0
-    while (1 << k) < n:
-        k += 1
-    return k - 13 if k > 13 else 0
-
-
-def _per_wg(n, ngroups, block, waves=4):
-    want = _cdiv(n * ngroups, waves * NUM_CU)
-    want = _cdiv(want, block) * block
-    return min(max(want, block), (8192 // block) * block)
-
-
-def _plan_1d(n, P, B, bw):
+# ------------------------------------------------------------------------------------------------ launch paths
+# The path the LOADED library plans for a case (ops.kde_plan: the launchers' own host code), in the format of the literals
+# the case lists carry.
+def _path_1d(n, P, B, bw):
     R = ops.kde_radius(bw)
-    small = n <= 65536
-    block = 256 if small else 1024
-    per_proj = 8 * B + 32
-    Pg = max(1, min(P, (52 * 1024 - 4 * B) // per_proj))
-    if small:
-        want = _cdiv(1024, _cdiv(n, block))
-        if want > 1:
-            pg_small = _cdiv(P, want)
-            if pg_small < 4:
-                pg_small = min(P, 4)
-            Pg = min(Pg, pg_small)
-    else:
-        Pg = _cdiv(P, _cdiv(P, Pg))
-    G = _cdiv(P, Pg)
-    w = block if small else _per_wg(n, G, block)
-    bblock = 512 if n >= 262144 else 256
-    ch = 1
-    while ch < 8 and ch * 2 <= P and _cdiv(n * ch, bblock) < 4 * NUM_CU:
-        ch *= 2
+    f, b = ops.kde_plan("kde1d_fwd", n, P, B, radius_x=R), ops.kde_plan("kde1d_bwd", n, P, B, radius_x=R)
+    assert f["window"] == b["window"]
+    Pg, G = f["Pg"], f["groups"]
     last = P - (G - 1) * Pg
-    win = "fact" if R == 4 else f"rt{R}"
-    return f"fwd{block}/Pg{Pg}x{G}{'' if last == Pg else f'(last{last})'}/w{w}/sh{_shift(n)}-bwd{bblock}/ch{ch}-{win}"
+    win = "fact" if f["window"] == 4 else f"rt{R}"
+    return (f"fwd{f['block']}/Pg{Pg}x{G}{'' if last == Pg else f'(last{last})'}/w{f['per_wg']}/sh{f['shift']}"
+            f"-bwd{b['block']}/ch{b['split']}-{win}")
 
 
-def _plan_2d(n, P, Bx, By, bwx, bwy):
+def _path_2d(n, P, Bx, By, bwx, bwy):
     rx, ry = ops.kde_radius(bwx), ops.kde_radius(bwy)
-    BB = Bx * By
-    per_proj, fixed = 8 * BB + 64, 4 * (Bx + By)
-    Pg = min(P, (max(60 * 1024, per_proj + fixed) - fixed) // per_proj)
-    G = _cdiv(P, Pg)
-    w = _per_wg(n, G, 1024)
-    for block, npt in ((1024, 4), (1024, 2), (1024, 1), (512, 1), (256, 1)):
-        if n // (block * npt) >= 2 * NUM_CU:
-            break
-    budget = 118 * 1024 if block >= 1024 else (59 * 1024 if block >= 512 else 30 * 1024)
-    bper = 4 * BB + 64
-    bPg = min(P, (max(budget, bper + fixed) - fixed) // bper)
-    win = "fact" if (rx, ry) == (4, 4) else f"rt{rx}x{ry}"
-    return f"fwd1024/Pg{Pg}x{G}/w{w}/sh{_shift(n)}-bwd{block}/npt{npt}/Pg{bPg}-{win}"
+    f, b = ops.kde_plan("kde2d_fwd", n, P, Bx, By, rx, ry), ops.kde_plan("kde2d_bwd", n, P, Bx, By, rx, ry)
+    assert f["window"] == b["window"]
+    win = "fact" if f["window"] == 4 else f"rt{rx}x{ry}"
+    return (f"fwd{f['block']}/Pg{f['Pg']}x{f['groups']}/w{f['per_wg']}/sh{f['shift']}"
+            f"-bwd{b['block']}/npt{b['split']}/Pg{b['Pg']}-{win}")
+
+
+def _fixed_point_plan(n):
+    """Forward plan of _centre_case_1d / _far_tail_case: one projection, 64 bins."""
+    return ops.kde_plan("kde1d_fwd", n, 1, 64)
 
 
 # ------------------------------------------------------------------------------------------------ fp64 references
@@ -171,7 +142,8 @@ def kde2d_bwd(x, V0, V1, cx, cy, sx, sy, rx, ry, gS, gx, accumulate):
 
 
 # ================================================================================================ A. 1-D KDE
-def _run_1d(dev, n, d, P, B, bw, seed, lo=-3.0, hi=3.0):
+def _run_1d(dev, n, d, P, B, bw, path, seed, lo=-3.0, hi=3.0):
+    assert _path_1d(n, P, B, bw) == path
     gen = torch.Generator().manual_seed(seed)
     x = torch.randn(n, d, generator=gen) * 1.2
     V = _dirs(P, d, gen)
@@ -189,23 +161,38 @@ def _run_1d(dev, n, d, P, B, bw, seed, lo=-3.0, hi=3.0):
         assert_grad(gx, go + g0.double().to(go.device) if acc else go)
 
 
-# (n, d, P, B, bandwidth in bins): every window variant (bw 0.5: radius-4 factorised; 0.3 / 0.6: run-time radius 3 / 5;
-# 0.12: radius 1), CH 1 / 2 / 4 / 8 through P, several projection groups with an uneven last one (P = 101), d = 1 .. 8
-CASES_1D = [(300, 1, 1, 64, 0.5), (257, 2, 2, 33, 0.3), (300, 3, 5, 40, 0.6), (150, 4, 9, 50, 0.12),
-            (200, 5, 101, 85, 0.5), (400, 6, 101, 85, 0.3), (129, 7, 3, 17, 0.45), (513, 8, 16, 128, 0.6),
-            # large-batch branch on the emulator: 1024-thread forward with several workgroups of > 1024 particles,
-            # shift > 0 and two equal groups of 51 / 50 projections; CH = 1 with 512-thread backward blocks at 300 000
-            (70001, 6, 101, 85, 0.5), (300000, 6, 4, 85, 0.3)]
+# (n, d, P, B, bandwidth in bins, launch path): every window variant (bw 0.5: radius-4 factorised; 0.3 / 0.6: run-time
+# radius 3 / 5; 0.12: radius 1), CH 1 / 2 / 4 / 8 through P, several projection groups with an uneven last one (P = 5, 9,
+# 101), d = 1 .. 8
+CASES_1D = [
+    (300, 1, 1, 64, 0.5, "fwd256/Pg1x1/w256/sh0-bwd256/ch1-fact"),
+    (257, 2, 2, 33, 0.3, "fwd256/Pg2x1/w256/sh0-bwd256/ch2-rt3"),
+    (300, 3, 5, 40, 0.6, "fwd256/Pg4x2(last1)/w256/sh0-bwd256/ch4-rt5"),
+    (150, 4, 9, 50, 0.12, "fwd256/Pg4x3(last1)/w256/sh0-bwd256/ch8-rt1"),
+    (200, 5, 101, 85, 0.5, "fwd256/Pg4x26(last1)/w256/sh0-bwd256/ch8-fact"),
+    (400, 6, 101, 85, 0.3, "fwd256/Pg4x26(last1)/w256/sh0-bwd256/ch8-rt3"),
+    (129, 7, 3, 17, 0.45, "fwd256/Pg3x1/w256/sh0-bwd256/ch2-fact"),
+    (513, 8, 16, 128, 0.6, "fwd256/Pg4x4/w256/sh0-bwd256/ch8-rt5"),
+    # large-batch branch on the emulator: 1024-thread forward, one particle per thread (w1024: workgroups of more
+    # particles than threads run in GPU_1D only), shift > 0 and two groups of 51 / 50 projections; 512-thread backward
+    # blocks at 300 000
+    (70001, 6, 101, 85, 0.5, "fwd1024/Pg51x2(last50)/w1024/sh4-bwd256/ch4-fact"),
+    (300000, 6, 4, 85, 0.3, "fwd1024/Pg4x1/w1024/sh6-bwd512/ch2-rt3"),
+]
 
 
-@pytest.mark.parametrize("n,d,P,B,bw", [pytest.param(*c, id=f"n{c[0]}-d{c[1]}-P{c[2]}-B{c[3]}-bw{c[4]}:" + _plan_1d(c[0], c[2], c[3], c[4]))
-                                        for c in CASES_1D])
-def test_kde1d_vs_fp64(backend, n, d, P, B, bw):
-    _run_1d(backend, n, d, P, B, bw, seed=n + 7 * d)
+def _params_1d(cases):
+    return [pytest.param(*c, id=f"n{c[0]}-d{c[1]}-P{c[2]}-B{c[3]}-bw{c[4]}:{c[5]}") for c in cases]
+
+
+@pytest.mark.parametrize("n,d,P,B,bw,path", _params_1d(CASES_1D))
+def test_kde1d_vs_fp64(backend, n, d, P, B, bw, path):
+    _run_1d(backend, n, d, P, B, bw, path, seed=n + 7 * d)
 
 
 # ================================================================================================ B. 2-D KDE
-def _run_2d(dev, n, d, P, Bx, By, bwx, bwy, seed):
+def _run_2d(dev, n, d, P, Bx, By, bwx, bwy, path, seed):
+    assert _path_2d(n, P, Bx, By, bwx, bwy) == path
     gen = torch.Generator().manual_seed(seed)
     x = torch.randn(n, d, generator=gen)
     V0, V1 = _dirs(P, d, gen), _dirs(P, d, gen)
@@ -225,20 +212,30 @@ def _run_2d(dev, n, d, P, Bx, By, bwx, bwy, seed):
         assert_grad(gx, go + g0.double().to(go.device) if acc else go)
 
 
-# (n, d, P, Bx, By, bwx, bwy): Bx != By; both axes factorised (s = 2 and 2.22); one axis factorised, the other at a
-# run-time radius (3 or 5); 85 x 85 images (one projection per group); d = 1 .. 8
-CASES_2D = [(300, 3, 3, 40, 24, 0.5, 0.5), (257, 2, 2, 31, 45, 0.45, 0.5), (200, 4, 3, 33, 20, 0.5, 0.3),
-            (150, 5, 2, 24, 36, 0.6, 0.5), (120, 6, 3, 85, 85, 0.5, 0.5), (100, 1, 2, 85, 85, 0.3, 0.6),
-            (90, 7, 5, 16, 11, 0.5, 0.5), (77, 8, 4, 12, 29, 0.45, 0.3),
-            # the large-batch launch shapes of the backward on the emulator: 512-thread blocks at 300 000 particles
-            (70001, 6, 3, 85, 85, 0.5, 0.5), (300000, 4, 2, 40, 24, 0.5, 0.3)]
+# (n, d, P, Bx, By, bwx, bwy, launch path): Bx != By; both axes factorised (s = 2 and 2.22); one axis factorised, the
+# other at a run-time radius (3 or 5); 85 x 85 images (one projection per group); d = 1 .. 8
+CASES_2D = [
+    (300, 3, 3, 40, 24, 0.5, 0.5, "fwd1024/Pg3x1/w1024/sh0-bwd256/npt1/Pg3-fact"),
+    (257, 2, 2, 31, 45, 0.45, 0.5, "fwd1024/Pg2x1/w1024/sh0-bwd256/npt1/Pg2-fact"),
+    (200, 4, 3, 33, 20, 0.5, 0.3, "fwd1024/Pg3x1/w1024/sh0-bwd256/npt1/Pg3-rt4x3"),
+    (150, 5, 2, 24, 36, 0.6, 0.5, "fwd1024/Pg2x1/w1024/sh0-bwd256/npt1/Pg2-rt5x4"),
+    (120, 6, 3, 85, 85, 0.5, 0.5, "fwd1024/Pg1x3/w1024/sh0-bwd256/npt1/Pg1-fact"),
+    (100, 1, 2, 85, 85, 0.3, 0.6, "fwd1024/Pg1x2/w1024/sh0-bwd256/npt1/Pg1-rt3x5"),
+    (90, 7, 5, 16, 11, 0.5, 0.5, "fwd1024/Pg5x1/w1024/sh0-bwd256/npt1/Pg5-fact"),
+    (77, 8, 4, 12, 29, 0.45, 0.3, "fwd1024/Pg4x1/w1024/sh0-bwd256/npt1/Pg4-rt4x3"),
+    # the large-batch launch shapes of the backward on the emulator: 512-thread blocks at 300 000 particles
+    (70001, 6, 3, 85, 85, 0.5, 0.5, "fwd1024/Pg1x3/w1024/sh4-bwd256/npt1/Pg1-fact"),
+    (300000, 4, 2, 40, 24, 0.5, 0.3, "fwd1024/Pg2x1/w1024/sh6-bwd512/npt1/Pg2-rt4x3"),
+]
 
 
-@pytest.mark.parametrize("n,d,P,Bx,By,bwx,bwy",
-                         [pytest.param(*c, id=f"n{c[0]}-d{c[1]}-P{c[2]}-{c[3]}x{c[4]}-bw{c[5]}x{c[6]}:" + _plan_2d(c[0], c[2], c[3], c[4], c[5], c[6]))
-                          for c in CASES_2D])
-def test_kde2d_vs_fp64(backend, n, d, P, Bx, By, bwx, bwy):
-    _run_2d(backend, n, d, P, Bx, By, bwx, bwy, seed=n + 11 * d)
+def _params_2d(cases):
+    return [pytest.param(*c, id=f"n{c[0]}-d{c[1]}-P{c[2]}-{c[3]}x{c[4]}-bw{c[5]}x{c[6]}:{c[7]}") for c in cases]
+
+
+@pytest.mark.parametrize("n,d,P,Bx,By,bwx,bwy,path", _params_2d(CASES_2D))
+def test_kde2d_vs_fp64(backend, n, d, P, Bx, By, bwx, bwy, path):
+    _run_2d(backend, n, d, P, Bx, By, bwx, bwy, path, seed=n + 11 * d)
 
 
 # ================================================================================================ C. fixed point
@@ -282,8 +279,12 @@ def _far_tail_case(dev, n, seed):
     assert float(rel.max()) <= 1e-4, (float(rel.max()), So[keep].min())
 
 
-@pytest.mark.parametrize("n", [8192, 8193], ids=lambda n: f"n{n}-sh{_shift(n)}")
-def test_fixed_point_centre_bin_exact(backend, n):
+FIXED_POINT = [(8192, "sh0"), (8193, "sh1")]
+
+
+@pytest.mark.parametrize("n,path", [pytest.param(n, p, id=f"n{n}-{p}") for n, p in FIXED_POINT])
+def test_fixed_point_centre_bin_exact(backend, n, path):
+    assert f"sh{_fixed_point_plan(n)['shift']}" == path
     _centre_case_1d(backend, n)
     _centre_case_2d(backend, n)
     _far_tail_case(backend, n, seed=n)
@@ -683,44 +684,89 @@ def hip():
     return torch.device("cuda", 0)
 
 
-GPU_1D = [(70001, 6, 101, 85, 0.5), (300000, 6, 101, 85, 0.3), (2097152, 6, 101, 85, 0.5), (2097152, 4, 25, 64, 0.6),
-          (300000, 1, 1, 64, 0.12), (70001, 8, 3, 85, 0.45)]
+GPU_1D = [
+    (70001, 6, 101, 85, 0.5, "fwd1024/Pg51x2(last50)/w1024/sh4-bwd256/ch4-fact"),
+    (300000, 6, 101, 85, 0.3, "fwd1024/Pg51x2(last50)/w1024/sh6-bwd512/ch2-rt3"),
+    (2097152, 6, 101, 85, 0.5, "fwd1024/Pg51x2(last50)/w4096/sh8-bwd512/ch1-fact"),
+    (2097152, 4, 25, 64, 0.6, "fwd1024/Pg25x1/w2048/sh8-bwd512/ch1-rt5"),
+    (300000, 1, 1, 64, 0.12, "fwd1024/Pg1x1/w1024/sh6-bwd512/ch1-rt1"),
+    (70001, 8, 3, 85, 0.45, "fwd1024/Pg3x1/w1024/sh4-bwd256/ch2-fact"),
+]
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("n,d,P,B,bw", [pytest.param(*c, id=f"n{c[0]}-d{c[1]}-P{c[2]}-B{c[3]}-bw{c[4]}:" + _plan_1d(c[0], c[2], c[3], c[4]))
-                                        for c in GPU_1D])
-def test_gpu_kde1d_vs_fp64(hip, n, d, P, B, bw):
-    _run_1d(hip, n, d, P, B, bw, seed=n + d)
+@pytest.mark.parametrize("n,d,P,B,bw,path", _params_1d(GPU_1D))
+def test_gpu_kde1d_vs_fp64(hip, n, d, P, B, bw, path):
+    _run_1d(hip, n, d, P, B, bw, path, seed=n + d)
 
 
-GPU_2D = [(70001, 6, 3, 85, 85, 0.5, 0.5), (300000, 6, 3, 85, 85, 0.5, 0.3), (600000, 5, 2, 40, 24, 0.5, 0.3),
-          (1048576, 6, 4, 40, 24, 0.5, 0.5),
-          (2097152, 6, 3, 85, 85, 0.5, 0.5), (2097152, 4, 4, 31, 45, 0.45, 0.6)]
-
-
-@pytest.mark.gpu
-@pytest.mark.parametrize("n,d,P,Bx,By,bwx,bwy",
-                         [pytest.param(*c, id=f"n{c[0]}-d{c[1]}-P{c[2]}-{c[3]}x{c[4]}-bw{c[5]}x{c[6]}:" + _plan_2d(c[0], c[2], c[3], c[4], c[5], c[6]))
-                          for c in GPU_2D])
-def test_gpu_kde2d_vs_fp64(hip, n, d, P, Bx, By, bwx, bwy):
-    _run_2d(hip, n, d, P, Bx, By, bwx, bwy, seed=n + d)
+GPU_2D = [
+    (70001, 6, 3, 85, 85, 0.5, 0.5, "fwd1024/Pg1x3/w1024/sh4-bwd256/npt1/Pg1-fact"),
+    (300000, 6, 3, 85, 85, 0.5, 0.3, "fwd1024/Pg1x3/w1024/sh6-bwd512/npt1/Pg2-rt4x3"),
+    (600000, 5, 2, 40, 24, 0.5, 0.3, "fwd1024/Pg2x1/w1024/sh7-bwd1024/npt1/Pg2-rt4x3"),
+    (1048576, 6, 4, 40, 24, 0.5, 0.5, "fwd1024/Pg4x1/w1024/sh7-bwd1024/npt2/Pg4-fact"),
+    (2097152, 6, 3, 85, 85, 0.5, 0.5, "fwd1024/Pg1x3/w6144/sh8-bwd1024/npt4/Pg3-fact"),
+    (2097152, 4, 4, 31, 45, 0.45, 0.6, "fwd1024/Pg4x1/w2048/sh8-bwd1024/npt4/Pg4-rt4x5"),
+]
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("n", [70001, 2097152, 16777216], ids=lambda n: f"n{n}-w{_per_wg(n, 1, 1024)}-sh{_shift(n)}")
-def test_gpu_fixed_point_centre_bin_exact(hip, n):
+@pytest.mark.parametrize("n,d,P,Bx,By,bwx,bwy,path", _params_2d(GPU_2D))
+def test_gpu_kde2d_vs_fp64(hip, n, d, P, Bx, By, bwx, bwy, path):
+    _run_2d(hip, n, d, P, Bx, By, bwx, bwy, path, seed=n + d)
+
+
+GPU_FIXED_POINT = [(70001, "w1024-sh4"), (2097152, "w2048-sh8"), (16777216, "w8192-sh11")]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,path", [pytest.param(n, p, id=f"n{n}-{p}") for n, p in GPU_FIXED_POINT])
+def test_gpu_fixed_point_centre_bin_exact(hip, n, path):
+    plan = _fixed_point_plan(n)
+    assert f"w{plan['per_wg']}-sh{plan['shift']}" == path
     _centre_case_1d(hip, n)
     _centre_case_2d(hip, n)
     _far_tail_case(hip, n, seed=n)
 
 
+_PATH_1D = re.compile(r"fwd(?P<fwd>\d+)/Pg(?P<Pg>\d+)x(?P<G>\d+)(\(last(?P<last>\d+)\))?/w(?P<w>\d+)/sh(?P<sh>\d+)"
+                      r"-bwd(?P<bwd>\d+)/ch(?P<ch>\d+)-(?P<win>fact|rt)\d*")
+_PATH_2D = re.compile(r"fwd(?P<fwd>\d+)/Pg(?P<Pg>\d+)x(?P<G>\d+)/w(?P<w>\d+)/sh(?P<sh>\d+)"
+                      r"-bwd(?P<bwd>\d+)/npt(?P<npt>\d+)/Pg(?P<bPg>\d+)-(?P<win>fact|rt)[\dx]*")
+
+
+def test_case_lists_cover_the_launch_paths():
+    """What the literals of the case lists cover, emulated and gpu-marked; no kernel runs here.  With the per-case equality of
+    _run_1d / _run_2d (literal == the library's plan) a removed case or a moved threshold fails instead of passing quietly."""
+    def fields(cases, pattern):
+        return [{k: v if k == "win" or v is None else int(v) for k, v in pattern.fullmatch(c[-1]).groupdict().items()}
+                for c in cases]
+
+    e1, e2, g1, g2 = fields(CASES_1D, _PATH_1D), fields(CASES_2D, _PATH_2D), fields(GPU_1D, _PATH_1D), fields(GPU_2D, _PATH_2D)
+    # the emulated lists
+    assert {f["fwd"] for f in e1} == {256, 1024}
+    assert {f["bwd"] for f in e1} == {256, 512}
+    assert {f["ch"] for f in e1} == {1, 2, 4, 8}
+    assert {"fwd": 256, "Pg": 4, "G": 2, "last": 1} in [{k: f[k] for k in ("fwd", "Pg", "G", "last")} for f in e1]     # small branch
+    assert {"fwd": 1024, "Pg": 51, "G": 2, "last": 50} in [{k: f[k] for k in ("fwd", "Pg", "G", "last")} for f in e1]  # large branch
+    assert {(f["bwd"], f["npt"]) for f in e2} == {(256, 1), (512, 1)}
+    for e in (e1, e2):
+        assert {f["sh"] for f in e} == {0, 4, 6}                                       # shift 0 and > 0
+        assert {f["win"] for f in e} == {"fact", "rt"}                                 # both windows, forward and backward
+        assert all(f["w"] == f["fwd"] for f in e)                                      # one particle per forward thread
+    assert {p for _, p in FIXED_POINT} == {"sh0", "sh1"}
+    # the gpu-marked lists, in addition
+    assert {(f["bwd"], f["npt"]) for f in g2} >= {(1024, 1), (1024, 2), (1024, 4)}
+    assert {f["w"] for f in g1 + g2 if f["w"] > f["fwd"]} == {2048, 4096, 6144}        # particles per workgroup above the block
+    assert {p for _, p in GPU_FIXED_POINT} >= {"w8192-sh11"}
+
+
 @pytest.mark.gpu
 def test_gpu_entropy_and_helpers_past_the_grid_cap(hip):
-    """Past the grid caps the kernels' stride loops wrap: entropy NUM_CU * 4 workgroups x 1024 particles, scale_rows 4096
-    x 1024 elements, gather 2048 x 256."""
-    _entropy_case(hip, NUM_CU * 4 * 1024 + 3, 6)
-    _entropy_case(hip, NUM_CU * 4 * 1024 + 3, 1)
+    """Past the grid caps the kernels' stride loops wrap: entropy 4 workgroups per CU (256 CUs) x 1024 particles, scale_rows
+    4096 x 1024 elements, gather 2048 x 256."""
+    _entropy_case(hip, 256 * 4 * 1024 + 3, 6)
+    _entropy_case(hip, 256 * 4 * 1024 + 3, 1)
     _scale_rows_case(hip, 4096 * 1024 // 6 + 5, 6)
     _scale_rows_case(hip, 4096 * 1024 + 5, 1)
     _gather_case(hip, 2048 * 256 + 7)

@@ -37,7 +37,9 @@ def one(kind: str, n: int):
         torch.cuda.synchronize()
         if it:
             tf += ev[0].elapsed_time(ev[1]); tb += ev[1].elapsed_time(ev[2])
-    return tf / reps, tb / reps, float(S.double().sum()), float(x.grad.double().abs().sum())
+    shape = (n, len(prob.transforms), bins) + ((bins,) if kind == "2d" else ())
+    plans = {k: ops.kde_plan(f"kde{kind}_{k}", *shape) for k in ("fwd", "bwd")}      # the launch shape that ran
+    return tf / reps, tb / reps, float(S.double().sum()), float(x.grad.double().abs().sum()), plans
 
 
 if __name__ == "__main__":
@@ -47,8 +49,9 @@ if __name__ == "__main__":
     ap.add_argument("--sweep", default=None)
     a = ap.parse_args()
     if a.sweep is None:
-        tf, tb, cs, cg = one(a.kind, a.n)
-        print(json.dumps({"fwd_ms": round(tf, 3), "bwd_ms": round(tb, 3), "sumS": cs, "sum|gx|": cg}))
+        tf, tb, cs, cg, plans = one(a.kind, a.n)
+        print(json.dumps({"fwd_ms": round(tf, 3), "bwd_ms": round(tb, 3), "sumS": cs, "sum|gx|": cg,
+                          "fwd_plan": plans["fwd"], "bwd_plan": plans["bwd"]}))
         sys.exit(0)
     if a.sweep == "1d":
         grid = [dict(MENTFLOW_KDE1D_BLOCK=b, MENTFLOW_KDE1D_LDS=l, MENTFLOW_KDE1D_WAVES=w)
