@@ -358,13 +358,46 @@ int mf_mcmc_ment_steps(float* x, int64_t chains, int d, int nslot, const float* 
  *                        over the merged quantile breakpoints with weights formed exactly in int64 (n1 * n2 < 2^63), and
  *                          dist[0] = (sum_s wpp[s] / P)^(1/p)   (fp32).
  *                        p >= 1 real (fast paths for 1 and 2).  A NaN anywhere in a row makes that wpp and dist NaN.
- *                        partial = mf_swd_cost_ws_doubles(P, n1, n2) doubles of scratch.                                    */
+ *                        partial = mf_swd_cost_ws_doubles(P, n1, n2) doubles of scratch.
+ *
+ * The adjoint (gradient of dist with respect to either point cloud; the directions are constants):
+ *
+ * mf_segsort_pairs_f32:  the same sort carrying each key's position: out[s, r] is bitwise what mf_segsort_f32 writes and
+ *                        perm[s, r] in [0, n) is the position in segment s of the key that ended up at rank r; perm[s, :] is
+ *                        always a permutation of 0..n-1 (also for rows of NaN, +-inf, +-0).  Order: ascending in the mapped
+ *                        key (-0.0 in front of +0.0, every NaN last), equal mapped keys by ascending position, i.e.
+ *                        torch.sort(stable=True) except that torch leaves mixed signed zeros in input order.  The unique
+ *                        64-bit composites (mapped key << 32 | position) are sorted, so the result does not depend on the
+ *                        network or merge order.  tile_log2 as above (0: the built-in pair tile, 2^12).
+ *                        `ws` = mf_segsort_pairs_workspace_bytes(P, n, tile_log2) bytes (0: none, -1: bad arguments), 8-byte
+ *                        aligned.  `out` may be `keys`.
+ * mf_swd_quantile_cost_bwd:  u[P, n1], v[P, n2] sorted per row and wpp[P] as mf_swd_quantile_cost left them, gdist[1] the
+ *                        gradient arriving at dist (device scalar; no device-to-host copy, no host synchronisation) ->
+ *                        gu[P, n1], gv[P, n2] = gdist * d dist / d u, d v.  With M = sum_s wpp[s] / P (the forward's order),
+ *                          coef = gdist (1/p) M^(1/p - 1) / P   (p = 1: gdist / P;  M == 0: coef = 0;  M NaN: all NaN),
+ *                        t = a - b one fp32 subtraction, then fp64: phi'(t) = sign(t) (p = 1), 2 t (p = 2), else
+ *                        p |t|^(p-1) sign(t); sign(0) = 0.  Equal sizes: g[r] = coef phi'(u_r - v_r) / n for u, the negative
+ *                        for v.  Unequal sizes: the sum over the quantile pieces an element takes part in, with the forward's
+ *                        int64 weights, divided by n1 n2 in fp64 and rounded once to fp32 (an element of the smaller set
+ *                        meets a contiguous range of the larger one, summed by a lane group in a fixed-shape fp64 tree: no
+ *                        atomics).  M == 0 (identical clouds) gives zero gradients by definition, where differentiating
+ *                        the composed formula gives 0 * inf = NaN for p > 1.  gu or gv may be NULL: that side is skipped.
+ *                        perm_u / perm_v (from mf_segsort_pairs_f32) != NULL: the value of rank r is stored at position
+ *                        perm[s, r] (the un-sort fused into the store); NULL: at r.
+ * mf_swd_project_bwd:    gx[i, k] (+)= sum_p dir[k, p] * g[p, i] for g[P, n], gx[n, d]: an fmaf chain over ascending p per
+ *                        output, no atomics; accumulate != 0 adds onto gx.  Limits of mf_swd_project.                        */
 int mf_swd_project(const float* x, int64_t n, int d, const float* dir, int P, float* u, void* stream);
 int64_t mf_segsort_workspace_bytes(int P, int64_t n, int tile_log2);
 int mf_segsort_f32(const float* keys, int P, int64_t n, int tile_log2, float* out, void* ws, void* stream);
 int64_t mf_swd_cost_ws_doubles(int P, int64_t n1, int64_t n2);
 int mf_swd_quantile_cost(const float* u, int64_t n1, const float* v, int64_t n2, int P, float p, double* partial, double* wpp,
                          float* dist, void* stream);
+int64_t mf_segsort_pairs_workspace_bytes(int P, int64_t n, int tile_log2);
+int mf_segsort_pairs_f32(const float* keys, int P, int64_t n, int tile_log2, float* out, int32_t* perm, void* ws, void* stream);
+int mf_swd_quantile_cost_bwd(const float* u, int64_t n1, const int32_t* perm_u, const float* v, int64_t n2,
+                             const int32_t* perm_v, int P, float p, const double* wpp, const float* gdist, float* gu, float* gv,
+                             void* stream);
+int mf_swd_project_bwd(const float* g, int64_t n, int d, const float* dir, int P, float* gx, int accumulate, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Sample-based entropy estimators  (mentflow/entropy.py:27-50).  Purely additive entry points: MF_ABI_VERSION stays 5.  Both

@@ -98,6 +98,10 @@ PROTOTYPES = {
     "mf_segsort_f32": (_i32, [_ptr, _i32, _i64, _i32, _ptr, _ptr, _ptr]),
     "mf_swd_cost_ws_doubles": (_i64, [_i32, _i64, _i64]),
     "mf_swd_quantile_cost": (_i32, [_ptr, _i64, _ptr, _i64, _i32, _f32, _ptr, _ptr, _ptr, _ptr]),
+    "mf_segsort_pairs_workspace_bytes": (_i64, [_i32, _i64, _i32]),
+    "mf_segsort_pairs_f32": (_i32, [_ptr, _i32, _i64, _i32, _ptr, _ptr, _ptr, _ptr]),
+    "mf_swd_quantile_cost_bwd": (_i32, [_ptr, _i64, _ptr, _ptr, _i64, _ptr, _i32, _f32, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "mf_swd_project_bwd": (_i32, [_ptr, _i64, _i32, _ptr, _i32, _ptr, _i32, _ptr]),
     "mf_knn_entropy_ws_bytes": (_i64, [_i64, _i32, _i32, _i32]),
     "mf_knn_entropy_fwd": (_i32, [_ptr, _i64, _i32, _i32, _i32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
     "mf_knn_entropy_bwd": (_i32, [_ptr, _i64, _i32, _ptr, _ptr, _ptr, _f32, _ptr, _ptr]),

@@ -2,7 +2,8 @@
 
 The reference hands the sorted-quantile cost of each projection to POT's CPU solver (``ot.lp.wasserstein_1d``); here the
 projections, a segmented key sort and the quantile integral are HIP kernels (mentflow_amd/csrc/swd.hip), and the
-distance comes back as a 0-dim device tensor without a device-to-host copy.  Evaluation only: it is not differentiable."""
+distance comes back as a 0-dim device tensor without a device-to-host copy.  SlicedWassersteindDistance is the evaluation
+metric of the reference's interface (no graph); SlicedWassersteinLoss is the same value with a backward pass in HIP."""
 from typing import Optional
 
 import torch
@@ -48,14 +49,15 @@ class SlicedWassersteindDistance:
         self.p = p
         self.device = device
 
-    def __call__(self, x1: torch.Tensor, x2: torch.Tensor, *, directions: Optional[torch.Tensor] = None) -> torch.Tensor:
+    @staticmethod
+    def _check_clouds(x1: torch.Tensor, x2: torch.Tensor) -> None:
         if x1.dim() != 2 or x2.dim() != 2:
             raise ValueError(f"x1 and x2 must be [N, d] point clouds (got {tuple(x1.shape)}, {tuple(x2.shape)})")
         if x1.shape[1] != x2.shape[1]:
             raise ValueError(f"x1.shape[1]={x1.shape} != x2.shape[1]={x2.shape})")
-        if torch.is_grad_enabled() and (x1.requires_grad or x2.requires_grad):
-            raise NotImplementedError("SlicedWassersteinDistance is an evaluation metric without a backward pass: call it under "
-                                      "torch.no_grad() or on detached samples")
+
+    def _directions(self, x1: torch.Tensor, x2: torch.Tensor, directions: Optional[torch.Tensor]) -> torch.Tensor:
+        """The remaining checks, and the directions[d, P] of this call (drawn unless given) as fp32 on x1's device."""
         d = x1.shape[1]
         if x1.shape[0] == 0 or x2.shape[0] == 0:
             raise ValueError(f"x1 and x2 need at least one point each (got {x1.shape[0]}, {x2.shape[0]})")
@@ -72,8 +74,30 @@ class SlicedWassersteindDistance:
             raise ValueError(f"directions must be [d={d}, P >= 1] (got {tuple(directions.shape)})")
         if directions.shape[1] * max(x1.shape[0], x2.shape[0]) >= 2**31:
             raise ValueError(f"{directions.shape[1]} projections of {max(x1.shape[0], x2.shape[0])} points reach 2^31 keys")
-        directions = directions.detach().to(x1.device, torch.float32)
+        return directions.detach().to(x1.device, torch.float32)
+
+    def __call__(self, x1: torch.Tensor, x2: torch.Tensor, *, directions: Optional[torch.Tensor] = None) -> torch.Tensor:
+        self._check_clouds(x1, x2)
+        if torch.is_grad_enabled() and (x1.requires_grad or x2.requires_grad):
+            raise NotImplementedError("SlicedWassersteinDistance is an evaluation metric without a backward pass: call it under "
+                                      "torch.no_grad() or on detached samples")
+        directions = self._directions(x1, x2, directions)
         return ops.sliced_wasserstein(x1.detach(), x2.detach(), directions, float(self.p))
 
 
 SlicedWassersteinDistance = SlicedWassersteindDistance
+
+
+class SlicedWassersteinLoss(SlicedWassersteindDistance):
+    """The same distance as a training loss: differentiable in x1 and x2 (ops.SlicedWassersteinFn; the adjoint is closed form,
+    HIP kernels, no atomics, reproducible bit for bit).  Same constructor, call signature, direction draw and
+    checks as SlicedWassersteindDistance; the directions are constants.  With grad enabled and an input that requires grad the
+    result is attached to the graph, otherwise it is exactly what the base class returns.  Identical clouds (distance 0) give
+    zero gradients, where autograd of the composed formula gives NaN for p > 1."""
+
+    def __call__(self, x1: torch.Tensor, x2: torch.Tensor, *, directions: Optional[torch.Tensor] = None) -> torch.Tensor:
+        self._check_clouds(x1, x2)
+        if not (torch.is_grad_enabled() and (x1.requires_grad or x2.requires_grad)):
+            return super().__call__(x1, x2, directions=directions)
+        directions = self._directions(x1, x2, directions)
+        return ops.SlicedWassersteinFn.apply(x1, x2, directions, float(self.p))

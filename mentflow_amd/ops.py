@@ -674,7 +674,8 @@ def mcmc_ment_steps(x: torch.Tensor, desc: torch.Tensor, meta: torch.Tensor, tab
 
 
 # ------------------------------------------------------------------------------------------------ sliced Wasserstein distance
-# Thin wrappers over mf_swd_* / mf_segsort_* (include/mentflow_hip.h).  Evaluation only: nothing here is differentiable.
+# Thin wrappers over mf_swd_* / mf_segsort_* (include/mentflow_hip.h).  sliced_wasserstein is the evaluation path (keys-only sort,
+# no graph); SlicedWassersteinFn at the end of the section is the differentiable one.
 def swd_project(x: torch.Tensor, directions: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """u[P, N] = (x[N, d] @ directions[d, P]).T, projection-major: each projection is one contiguous segment."""
     x, directions = _f32c(x), _f32c(directions)
@@ -734,3 +735,115 @@ def sliced_wasserstein(x1: torch.Tensor, x2: torch.Tensor, directions: torch.Ten
         segmented_sort(u1, out=u1)
         segmented_sort(u2, out=u2)
     return swd_quantile_cost(u1, u2, p)[1]
+
+
+def segmented_sort_pairs(keys: torch.Tensor, out: Optional[torch.Tensor] = None, perm: Optional[torch.Tensor] = None,
+                         _tile_log2: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(sorted, perm): segmented_sort's values bit for bit, and perm[s, r] (int32) = the position in row s of the key at rank r:
+    ascending mapped keys (-0.0 before +0.0, NaN last), ties by ascending position; always a permutation.  `out` may be `keys`."""
+    keys = _f32c(keys)
+    if keys.dim() != 2:
+        raise ValueError(f"segmented_sort_pairs: keys[P, N] expected (got {tuple(keys.shape)})")
+    P, n = keys.shape
+    if out is None:
+        out = torch.empty_like(keys)
+    if perm is None:
+        perm = torch.empty(P, n, dtype=torch.int32, device=keys.device)
+    nbytes = int(_lib.get_lib().mf_segsort_pairs_workspace_bytes(P, n, int(_tile_log2)))
+    ws = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=keys.device) if nbytes > 0 else None
+    call("mf_segsort_pairs_f32", ptr(keys), P, n, int(_tile_log2), ptr(out), ptr(perm), ptr(ws), stream_ptr(keys))
+    return out, perm
+
+
+def swd_quantile_cost_bwd(u: torch.Tensor, v: torch.Tensor, wpp: torch.Tensor, gdist: torch.Tensor, p: float = 2.0,
+                          perm_u: Optional[torch.Tensor] = None, perm_v: Optional[torch.Tensor] = None,
+                          need_u: bool = True, need_v: bool = True) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """(gu[P, N1], gv[P, N2]) = gdist * d dist / d (u, v) for the sorted rows and wpp of swd_quantile_cost; gdist is a device
+    scalar.  With perm_* (segmented_sort_pairs) the gradient of rank r is stored at position perm[s, r], i.e. in the order of
+    the unsorted rows; a side that is not needed is None."""
+    u, v = _f32c(u), _f32c(v)
+    if u.dim() != 2 or v.dim() != 2 or u.shape[0] != v.shape[0]:
+        raise ValueError(f"swd_quantile_cost_bwd: u[P, N1] and v[P, N2] expected (got {tuple(u.shape)}, {tuple(v.shape)})")
+    P = u.shape[0]
+    if wpp.dtype != torch.float64 or wpp.numel() != P or not wpp.is_contiguous():
+        raise ValueError(f"swd_quantile_cost_bwd: wpp[{P}] float64 expected (got {wpp.dtype}{tuple(wpp.shape)})")
+    gdist = _f32c(gdist)
+    if gdist.numel() != 1:
+        raise ValueError(f"swd_quantile_cost_bwd: gdist must hold one value (got {tuple(gdist.shape)})")
+    for t, side in ((perm_u, u), (perm_v, v)):
+        if t is not None and (t.dtype != torch.int32 or t.shape != side.shape or not t.is_contiguous()):
+            raise ValueError(f"swd_quantile_cost_bwd: perm must be contiguous int32{tuple(side.shape)} (got {t.dtype}{tuple(t.shape)})")
+    gu = torch.empty_like(u) if need_u else None
+    gv = torch.empty_like(v) if need_v else None
+    call("mf_swd_quantile_cost_bwd", ptr(u), u.shape[1], ptr(perm_u), ptr(v), v.shape[1], ptr(perm_v), P, float(p), ptr(wpp),
+         ptr(gdist), ptr(gu), ptr(gv), stream_ptr(u))
+    return gu, gv
+
+
+def swd_project_bwd(g: torch.Tensor, directions: torch.Tensor, out: Optional[torch.Tensor] = None,
+                    accumulate: bool = False) -> torch.Tensor:
+    """gx[N, d] (+)= g[P, N].T @ directions[d, P].T: the adjoint of swd_project with respect to the points."""
+    g, directions = _f32c(g), _f32c(directions)
+    if g.dim() != 2 or directions.dim() != 2 or directions.shape[1] != g.shape[0]:
+        raise ValueError(f"swd_project_bwd: g[P, N] and directions[d, P] expected (got {tuple(g.shape)}, {tuple(directions.shape)})")
+    P, n = g.shape
+    d = directions.shape[0]
+    if out is None:
+        if accumulate:
+            raise ValueError("swd_project_bwd: accumulate needs the buffer to add onto")
+        out = torch.empty(n, d, dtype=_F32, device=g.device)
+    elif out.dtype != _F32 or tuple(out.shape) != (n, d) or not out.is_contiguous():
+        raise ValueError(f"swd_project_bwd: out[{n}, {d}] contiguous float32 expected (got {out.dtype}{tuple(out.shape)})")
+    call("mf_swd_project_bwd", ptr(g), n, d, ptr(directions), P, ptr(out), int(bool(accumulate)), stream_ptr(g))
+    return out
+
+
+class SlicedWassersteinFn(torch.autograd.Function):
+    """dist = sliced_wasserstein(x1, x2, directions, p), differentiable in x1 and x2 (the directions are constants).
+
+    Forward: projections, a pair sort (keys with their positions) for each side that needs a gradient and the keys-only sort
+    for the other, the quantile cost.  Equal sizes with both gradients wanted: one [2P, N] buffer, one launch sequence.
+    Backward: the closed-form adjoint of the cost stored straight into unsorted order, then the back-projection; no atomics,
+    so two backward passes give the same bits.  Identical clouds give zero gradients (include/mentflow_hip.h)."""
+
+    @staticmethod
+    def forward(ctx, x1, x2, directions, p, _tile_log2=0):
+        x1, x2, directions = _f32c(x1.detach()), _f32c(x2.detach()), _f32c(directions.detach())
+        P = directions.shape[1]
+        need1, need2 = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        perm1 = perm2 = None
+        if x1.shape[0] == x2.shape[0] and need1 == need2:
+            u = torch.empty(2 * P, x1.shape[0], dtype=_F32, device=x1.device)
+            swd_project(x1, directions, out=u[:P])
+            swd_project(x2, directions, out=u[P:])
+            if need1:
+                perm = segmented_sort_pairs(u, out=u, _tile_log2=_tile_log2)[1]
+                perm1, perm2 = perm[:P], perm[P:]
+            else:
+                segmented_sort(u, out=u, _tile_log2=_tile_log2)
+            u1, u2 = u[:P], u[P:]
+        else:
+            u1 = swd_project(x1, directions)
+            u2 = swd_project(x2, directions)
+            if need1:
+                perm1 = segmented_sort_pairs(u1, out=u1, _tile_log2=_tile_log2)[1]
+            else:
+                segmented_sort(u1, out=u1, _tile_log2=_tile_log2)
+            if need2:
+                perm2 = segmented_sort_pairs(u2, out=u2, _tile_log2=_tile_log2)[1]
+            else:
+                segmented_sort(u2, out=u2, _tile_log2=_tile_log2)
+        wpp, dist = swd_quantile_cost(u1, u2, p)
+        ctx.p = float(p)
+        ctx.saved = (u1, u2, perm1, perm2, wpp, directions)          # made here, seen by nobody else: no version checks needed
+        return dist
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gdist):
+        u1, u2, perm1, perm2, wpp, directions = ctx.saved
+        need1, need2 = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        gu1, gu2 = swd_quantile_cost_bwd(u1, u2, wpp, gdist, ctx.p, perm_u=perm1, perm_v=perm2, need_u=need1, need_v=need2)
+        gx1 = swd_project_bwd(gu1, directions) if need1 else None
+        gx2 = swd_project_bwd(gu2, directions) if need2 else None
+        return gx1, gx2, None, None, None
