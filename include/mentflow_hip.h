@@ -340,6 +340,24 @@ int mf_mcmc_ment_steps(float* x, int64_t chains, int d, int nslot, const float* 
                        float* out, int32_t* accepted, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Differentiable log-density of classical MENT (no counterpart in the reference, whose interpolators are scipy on the host).
+ * A purely additive entry point: MF_ABI_VERSION stays 5.  Slot arguments (nslot .. prior_lognorm) and limits exactly as
+ * mf_ment_prob takes them; n = 0 and nslot = 0 are valid.
+ *
+ * mf_ment_logprob: logp[i] = sum_s log clamp(h_s(x_i), 0, 1e10) + log prior(x_i)  (prior_kind 0: + 0; 1: + prior_lognorm -
+ *                  |x|^2 / (2 prior_a^2); 2: + prior_lognorm inside [-prior_a, prior_a]^d, -inf outside).  Projections and
+ *                  cells are those of mf_ment_prob bit for bit, slot order and early exit included: logp = -inf exactly where
+ *                  that product meets a zero factor first, NaN where it meets a NaN factor first; where the fp32 product would
+ *                  merely underflow or overflow, logp stays finite and accurate (the factors' exponents are summed apart).
+ *                  grad (may be NULL) [n, d] = d logp / dx = sum_s (h_s' / h_s) rows_s + d log prior / dx, with the derivative
+ *                  of the cell that holds the point (the right derivative at an interior bin centre, the left one at the last
+ *                  centre); a slot with h_s >= 1e10 (on the clamp) contributes nothing; a row with logp = -inf gets 0, a row
+ *                  with logp = NaN gets NaN.  Tables are constants.  No atomics; rows are independent; bitwise reproducible. */
+int mf_ment_logprob(const float* x, int64_t n, int d, int nslot, const float* desc, const int32_t* meta, const float* tables,
+                    int64_t table_floats, int prior_kind, float prior_a, float prior_lognorm, float* logp, float* grad,
+                    void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Sliced Wasserstein distance  (mentflow/loss.py:20-42, where the 1-D transport cost is POT's ot.lp.wasserstein_1d on the
  * host).  Purely additive entry points: MF_ABI_VERSION stays 5.  No float atomics, fp64 sums in a fixed order: every output
  * is bitwise reproducible.  All sizes obey P * n < 2^31.

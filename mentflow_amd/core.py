@@ -169,7 +169,7 @@ class MENTFlow(nn.Module):
                                           ops.kde_radius(diagnostic.bandwidth_bins[1]))
             pieces.append(S.reshape(-1))
         if use_entropy:
-            pieces.append(ops.EntropySumsFn.apply(x, log_prob))
+            pieces.append(self.entropy_estimator.sums(x, log_prob))
         if mfdist.is_active():
             flat = mfdist.all_reduce_sum(torch.cat(pieces))
             sizes = [p.numel() for p in pieces]
@@ -200,7 +200,7 @@ class MENTFlow(nn.Module):
 
     def _loss_generic_data_parallel(self, n_total: int):
         """The generic loop (core.py:113-117) with the particle batch sharded over the ranks: every histogram diagnostic is a
-        sum over particles followed by a normalisation, so the ranks all-reduce the raw sums of ALL measurements (and the two
+        sum over particles followed by a normalisation, so the ranks all-reduce the raw sums of ALL measurements (and the
         entropy sums) in ONE buffer and evaluate normalisation, discrepancy callable and loss redundantly — (L, H, D) are
         the single-process values on the concatenated batch, identical on every rank.  A diagnostic or an entropy estimator
         without a sum form raises, naming itself."""
@@ -218,7 +218,7 @@ class MENTFlow(nn.Module):
         shapes = [p.shape for p in pieces]
         flat = [p.reshape(-1) for p in pieces]
         if use_entropy:
-            flat.append(ops.EntropySumsFn.apply(x, log_prob))
+            flat.append(est.sums(x, log_prob))
         reduced = torch.split(mfdist.all_reduce_sum(torch.cat(flat)), [f.numel() for f in flat])
         predictions = finish([r.reshape(sh) for r, sh in zip(reduced, shapes)], n_total)
         D = self.discrepancy_vector(predictions)

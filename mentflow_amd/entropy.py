@@ -64,16 +64,28 @@ class KNNEntropyEstimator(EntropyEstimator):
 class MonteCarloEntropyEstimator(EntropyEstimator):
     """H = mean(log_prob) - mean(prior.log_prob(x))  (entropy.py:53-62), both means from one reduction kernel.
 
-    ``from_sums`` finishes the estimate from already reduced sums — used by ``MENTFlow.loss`` so that a data-parallel
-    run can sum [sum log_prob, sum |x|^2] across GPUs first."""
+    ``sums`` reduces the particles at hand and ``from_sums`` finishes the estimate from already reduced sums — used by
+    ``MENTFlow.loss`` so that a data-parallel run can sum across GPUs in between.  For ``prior.Gaussian`` (or no prior) the
+    sums are [sum log_prob, sum |x|^2], the prior's sufficient statistic.  Any other prior with a differentiable
+    ``log_prob(x)`` (``prior.MENTPrior``, ``ment.UniformPrior``) adds a third entry, sum prior.log_prob(x), from the same
+    fixed-order fp64 reduction and its adjoint."""
+
+    def sums(self, x: torch.Tensor, log_prob: torch.Tensor) -> torch.Tensor:
+        out = ops.EntropySumsFn.apply(x, log_prob)
+        if self.prior is None or isinstance(self.prior, Gaussian):
+            return out
+        return torch.cat([out, ops.EntropySumsFn.apply(x, self.prior.log_prob(x))[:1]])
 
     def from_sums(self, sums: torch.Tensor, n_total: int) -> torch.Tensor:
         H = sums[0] / n_total
+        if sums.numel() == 3:
+            return H - sums[2] / n_total
         if self.prior is not None:
             if not isinstance(self.prior, Gaussian):
-                raise NotImplementedError("only the Gaussian prior is on the hot path (SURVEY.md §2 row 7)")
+                raise NotImplementedError(f"prior {type(self.prior).__name__}: its sum is the third entry of sums(), "
+                                          "which these two entries lack")
             H = H - (-0.5 * sums[1] / (n_total * self.prior.scale ** 2) + self.prior.log_norm())
         return H
 
     def forward(self, x: torch.Tensor, log_prob: torch.Tensor) -> torch.Tensor:
-        return self.from_sums(ops.EntropySumsFn.apply(x, log_prob), x.shape[0])
+        return self.from_sums(self.sums(x, log_prob), x.shape[0])

@@ -10,6 +10,10 @@ a SLOT of one fused kernel launch per pre-transform chain: its projection rows `
 centre grid and the table go to the kernel, which evaluates all slots per point.  Any other pair is evaluated in torch on the
 device (transform, ``diagnostic.project``, ``LagrangeFunction``): same values, not fused.
 
+``MENT.log_density`` (not in the reference) is the logarithm of that density as a sum of logarithms, differentiable in x, on the
+kernel of mentflow_amd/csrc/ment_logp.hip: finite where the fp32 product has left its range, and what ``prior.MENTPrior`` and a
+reverse-KL fit of a flow to a MENT solution are built on.
+
 Deliberate differences from the reference (each a bug or a CPU-only limit there):
   - ``simulate_all`` in integrate mode integrates every slot (the reference calls a missing ``simulate_integrate``);
   - integrate mode handles 2-D slots (the reference reshapes with ``diagnostic.shape``, which its Histogram2D lacks);
@@ -324,8 +328,25 @@ class MENT:
                 off += m[1] * m[2]
             chain.desc_t = torch.tensor(chain.desc, dtype=torch.float32).reshape(-1, ops.MENT_DESC).to(dev)
             chain.meta_t = torch.tensor(meta, dtype=torch.int32).reshape(-1, 4).to(dev)
-        self._plan = (list(chains.values()), torch_slots, dev)
+        self._plan = (list(chains.values()), torch_slots, dev, {})
         return self._plan[0], self._plan[1]
+
+    def _torch_slot_args(self, i: int, j: int):
+        """(desc, meta) that hand a slot outside the chains to the log-density kernel on its projected coordinates (identity
+        rows), or None when its centres are not uniform (_interp_torch then).  Decided once per plan: the test of the centres
+        reads them on the host."""
+        cache = self._plan[3]
+        if (i, j) not in cache:
+            lf = self.lagrange_functions[i][j]
+            args = None
+            if lf.uniform():
+                coords = lf.coord_list()
+                dim = len(coords)
+                desc, meta = _slot_rows([torch.eye(dim)[k] for k in range(dim)], coords, dim)
+                args = (torch.tensor([desc], dtype=torch.float32).to(self._plan[2]),
+                        torch.tensor([meta + [0]], dtype=torch.int32).to(self._plan[2]))
+            cache[(i, j)] = args
+        return cache[(i, j)]
 
     def _tables(self, chain: _Chain) -> torch.Tensor:
         if not chain.slots:
@@ -340,6 +361,52 @@ class MENT:
 
     def log_prob(self, x: torch.Tensor, pad: float = 1.00e-12) -> torch.Tensor:
         return torch.log(self.prob(x) + pad)
+
+    def log_density(self, x: torch.Tensor, pad: float = 0.0) -> torch.Tensor:
+        """log of the (unnormalised) density of ``prob``, differentiable in x: the sum over all slots of log clamp(h, 0, 1e10)
+        plus ``prior.log_prob(x)``, from ops.MentLogProbFn per pre-transform chain (autograd runs through the chain's
+        pre-transforms) and, for the slots outside the chains, from the same kernel on their projected coordinates or from
+        ``_interp_torch`` when their centres are not uniform.
+
+        Where ``log_prob`` is log(prob + pad) of an fp32 product — the constant log(pad) once a hundred factors have
+        underflowed — this sums logarithms: finite and accurate wherever every factor is positive.  Outside the support the
+        value is -inf and the gradient row 0 (nothing pulls such a point); a NaN coordinate gives NaN in both.  The derivative
+        is that of the cell which holds the point: the right derivative at an interior bin centre, the left one at the last
+        centre.  The Lagrange functions are constants here.  ``pad > 0`` returns logaddexp(log_density, log pad), which is
+        log(prob + pad) wherever that is representable.  No host synchronisation: the call can be captured in a graph."""
+        chains, torch_slots = self._get_plan()
+        x = x.to(torch.float32)
+        prior = _prior_args(self.prior)
+        total = None
+        for chain in chains:
+            xin = apply_pre(x, chain.pre) if chain.pre else x
+            lp = ops.MentLogProbFn.apply(xin.contiguous(), chain.desc_t, chain.meta_t, self._tables(chain),
+                                         prior if total is None else (0, 0.0, 0.0))
+            total = lp if total is None else total + lp
+        transported = {}
+        for i, j in torch_slots:
+            if i not in transported:
+                transported[i] = self.transforms[i](x)
+            lf = self.lagrange_functions[i][j]
+            coords = lf.coord_list()
+            u = self.diagnostics[i][j].project(transported[i]).reshape(x.shape[0], len(coords)).to(torch.float32)
+            args = self._torch_slot_args(i, j)
+            if args is not None:
+                lp = ops.MentLogProbFn.apply(u.contiguous(), args[0], args[1],
+                                             lf.values.to(u.device, torch.float32).reshape(-1).contiguous(), (0, 0.0, 0.0))
+            else:
+                h = _interp_torch(coords, lf.values, u)
+                zero = h <= 0.0                            # outside the hull, a zero of the table (or a negative entry)
+                top = h >= 1.0e10                          # on the upper clamp: a constant
+                lp = torch.log(torch.where(zero | top, torch.ones_like(h), h))
+                lp = torch.where(top, torch.full_like(h, math.log(1.0e10)), lp)
+                lp = torch.where(zero, torch.full_like(h, float("-inf")), lp)
+            total = total + lp
+        # a row that any term puts outside the support takes no gradient through the terms that are finite there
+        total = torch.where(torch.isneginf(total), torch.full_like(total, float("-inf")), total)
+        if pad > 0.0:
+            total = torch.logaddexp(total, torch.full_like(total, math.log(pad)))
+        return total
 
     def prob(self, x: torch.Tensor) -> torch.Tensor:
         chains, torch_slots = self._get_plan()

@@ -673,6 +673,50 @@ def mcmc_ment_steps(x: torch.Tensor, desc: torch.Tensor, meta: torch.Tensor, tab
          ptr(out), ptr(accepted), stream_ptr(x))
 
 
+def ment_logprob(x: torch.Tensor, desc: torch.Tensor, meta: torch.Tensor, tables: torch.Tensor, prior=(0, 0.0, 0.0),
+                 want_grad: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """(logp[n], grad[n, d] or None) of mf_ment_logprob (include/mentflow_hip.h): the sum over slots of log clamp(h, 0, 1e10)
+    at x[n, d] plus the log-prior, and its gradient with respect to x.  -inf outside the support (gradient row 0), NaN for a NaN
+    coordinate (gradient row NaN); finite where the product of ment_prob under- or overflows."""
+    if x.dim() != 2 or not 1 <= x.shape[1] <= 8:
+        raise RuntimeError(f"ment_logprob: x[n, d <= 8] expected (got {tuple(x.shape)})")
+    x, tables = _f32c(x), _f32c(tables)
+    nslot = desc.shape[0]
+    if desc.dtype != _F32 or tuple(desc.shape) != (nslot, MENT_DESC) or meta.dtype != torch.int32 or tuple(meta.shape) != (nslot, 4):
+        raise RuntimeError(f"ment_logprob: desc float32[nslot, {MENT_DESC}] and meta int32[nslot, 4] expected (got "
+                           f"{desc.dtype}{tuple(desc.shape)}, {meta.dtype}{tuple(meta.shape)})")
+    for t in (desc, meta, tables):
+        if t.device != x.device:
+            raise RuntimeError(f"ment_logprob: all tensors must be on {x.device} (got one on {t.device})")
+    n, d = x.shape
+    logp = torch.empty(n, dtype=_F32, device=x.device)
+    grad = torch.empty(n, d, dtype=_F32, device=x.device) if want_grad else None
+    call("mf_ment_logprob", ptr(x), n, d, nslot, ptr(desc), ptr(meta), ptr(tables), tables.numel(), int(prior[0]),
+         float(prior[1]), float(prior[2]), ptr(logp), ptr(grad), stream_ptr(x))
+    return logp, grad
+
+
+class MentLogProbFn(torch.autograd.Function):
+    """x[n, d] -> logp[n] of ment_logprob, differentiable in x: one kernel launch computes the value and, when x needs a gradient,
+    d logp / dx, which the backward scales by the incoming gradient.  Rows with logp = -inf pass no gradient whatever comes in
+    (0 * inf would be NaN).  Tables, descriptors and the prior are constants; the backward is not differentiable again."""
+
+    @staticmethod
+    def forward(ctx, x, desc, meta, tables, prior):
+        want = bool(ctx.needs_input_grad[0])
+        logp, grad = ment_logprob(x, desc, meta, tables, prior, want_grad=want)
+        if want:
+            ctx.save_for_backward(grad, logp)
+        return logp
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        grad, logp = ctx.saved_tensors
+        gx = torch.where(torch.isneginf(logp)[:, None], torch.zeros_like(grad), g[:, None] * grad)
+        return gx, None, None, None, None
+
+
 # ------------------------------------------------------------------------------------------------ sliced Wasserstein distance
 # Thin wrappers over mf_swd_* / mf_segsort_* (include/mentflow_hip.h).  sliced_wasserstein is the evaluation path (keys-only sort,
 # no graph); SlicedWassersteinFn at the end of the section is the differentiable one.

@@ -1,4 +1,5 @@
 """Prior distributions (interface of mentflow/prior.py:4-26)."""
+import copy
 import math
 
 import torch
@@ -22,3 +23,34 @@ class Gaussian:
 
     def log_prob(self, x: torch.Tensor) -> torch.Tensor:
         return self.log_norm() - 0.5 * x.square().sum(dim=1) / self.scale ** 2
+
+
+class MENTPrior:
+    """A classical MENT reconstruction (``ment.MENT``: an earlier run with fewer views, other optics, a coarser scan) as the
+    prior of ``MonteCarloEntropyEstimator``: ``log_prob(x) = ment.log_density(x, pad)``, differentiable in x on the
+    log-density kernel (no counterpart in the reference).
+
+    The density is UNNORMALISED: MENT fixes its Lagrange functions up to the normalisation Z of their product, so the
+    relative entropy H comes out offset by the unknown constant log Z, which moves no gradient.  With ``pad > 0`` a point
+    outside the support of the reconstruction carries the constant log(pad) with zero gradient (with ``pad = 0``: -inf, which
+    makes H infinite as soon as one particle leaves the support).
+
+    Picklable (``MENTFlow.save`` stores the entropy estimator with its prior): the MENT's cached launch plan is dropped and
+    rebuilt on first use."""
+
+    def __init__(self, ment, pad: float = 1.0e-12) -> None:
+        self.ment, self.pad = ment, float(pad)
+
+    def to(self, device) -> "MENTPrior":
+        self.ment.to(device)
+        return self
+
+    def log_prob(self, x: torch.Tensor) -> torch.Tensor:
+        return self.ment.log_density(x, self.pad)
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        ment = copy.copy(self.ment)
+        ment._plan = None
+        state["ment"] = ment
+        return state
