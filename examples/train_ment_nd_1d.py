@@ -3,10 +3,12 @@ experiments/rec_nd_1d/train_ment.py setting) on the MI355X: measurements from me
 res 33, sample mode with 1 M samples per sub-step, MENTTrainer with an mf.Evaluator as its eval hook: per epoch it prints the mean
 KL discrepancy of 50 000 model samples and their sliced Wasserstein distance (50 projections, p = 2) to 50 000 fresh
 ground-truth samples, as experiments/rec_nd_1d/setup.py::setup_eval does.  `--sampler mh` draws the particles from
-Metropolis-Hastings chains (mentflow_amd.sample.MetropolisHastingsSampler) instead of the dense grid.
+Metropolis-Hastings chains (mentflow_amd.sample.MetropolisHastingsSampler) instead of the dense grid, `--sampler mala` from
+Metropolis-adjusted Langevin chains (mentflow_amd.sample.LangevinSampler), whose proposals follow the gradient of the log-density.
 
     python examples/train_ment_nd_1d.py [--epochs 5] [--num 50] [--res 33]
     python examples/train_ment_nd_1d.py --sampler mh [--chains 65536] [--step 0.25] [--burn 200] [--thin 10]
+    python examples/train_ment_nd_1d.py --sampler mala [--drift-clip 1.0] [--chains 65536] [--step 0.25] [--burn 200] [--thin 10]
 """
 import argparse
 import os
@@ -20,7 +22,7 @@ import mentflow_amd as mf  # noqa: E402
 from mentflow_amd.distributions import get_distribution  # noqa: E402
 from mentflow_amd.harness import build_problem  # noqa: E402
 from mentflow_amd.ment import MENT  # noqa: E402
-from mentflow_amd.sample import GridSampler, MetropolisHastingsSampler  # noqa: E402
+from mentflow_amd.sample import GridSampler, LangevinSampler, MetropolisHastingsSampler  # noqa: E402
 from mentflow_amd.train import MENTTrainer  # noqa: E402
 
 
@@ -32,11 +34,12 @@ def main():
     ap.add_argument("--res", type=int, default=33)
     ap.add_argument("--samples", type=int, default=1_000_000)
     ap.add_argument("--eval-size", type=int, default=50_000)
-    ap.add_argument("--sampler", choices=("grid", "mh"), default="grid")
+    ap.add_argument("--sampler", choices=("grid", "mh", "mala"), default="grid")
     ap.add_argument("--chains", type=int, default=65536)
     ap.add_argument("--step", type=float, default=0.25)
     ap.add_argument("--burn", type=int, default=200)
     ap.add_argument("--thin", type=int, default=10)
+    ap.add_argument("--drift-clip", type=float, default=1.0, help="mala: bound of the drift per axis, in proposal standard deviations")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     ndim, xmax = 4, 4.0
@@ -44,6 +47,9 @@ def main():
                          prior_scale=3.0, device=dev, meas_samples=1_000_000)
     if args.sampler == "grid":
         sampler = GridSampler(limits=ndim * [(-xmax, xmax)], shape=ndim * [args.res], noise=1.0)
+    elif args.sampler == "mala":
+        sampler = LangevinSampler(ndim, chains=args.chains, step=args.step, burn=args.burn, thin=args.thin, start_scale=0.5,
+                                  drift_clip=args.drift_clip)
     else:               # chains started inside the support: a chain that starts outside it walks freely and may not return
         sampler = MetropolisHastingsSampler(ndim, chains=args.chains, step=args.step, burn=args.burn, thin=args.thin,
                                             start_scale=0.5)

@@ -340,6 +340,32 @@ int mf_mcmc_ment_steps(float* x, int64_t chains, int d, int nslot, const float* 
                        float* out, int32_t* accepted, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Metropolis-adjusted Langevin chains on the density of classical MENT (no counterpart in the reference).  A purely additive
+ * entry point: MF_ABI_VERSION stays 5.  Slot arguments (nslot .. prior_lognorm) exactly as mf_ment_prob takes them; x, noise,
+ * steps, step_offset, scale, keep_from, keep_every, out and accepted exactly as mf_mcmc_ment_steps takes them.
+ *
+ * mf_mala_ment_steps: `chains` independent chains, one GPU lane each, advance `steps` steps from x[chains, d] (in / out).  With
+ *                     l = logp(x) and g = d logp / dx as mf_ment_logprob returns them (the same device function: the same
+ *                     bits), s = scale[a], z = noise[t][a][c], u = noise[t][d][c], all in fp32:
+ *                       drift_a(x) = min(max(0.5 s^2 g_a(x), -drift_clip s), drift_clip s)
+ *                       y_a = fma(s, z, x_a + drift_a(x)),   r_a = ((x_a - y_a) - drift_a(y)) / s,
+ *                       D = (logp(y) - l) + 0.5 (sum_a z^2 - sum_a r_a^2),
+ *                       accept iff  logp(y) > -inf ? (l == -inf || log u < D) : (logp(y) == -inf && l == -inf),
+ *                     and never when logp(y), u or a z is NaN.  So a chain never leaves the support once inside; outside it
+ *                     (l == -inf, g == 0: no drift) it random-walks and takes the first point inside; a state never turns NaN;
+ *                     u == 0 accepts whenever D > -inf.  The test is made on logarithms: it stays the Metropolis rule where
+ *                     the fp32 product of mf_ment_prob under- or overflows.  drift_clip >= 0 (0: a driftless walk) bounds the
+ *                     drift per axis in proposal standard deviations; the truncated drift is a function of the state alone,
+ *                     so the correction is exact.  l and g are recomputed at entry.  logp (may be NULL) [chains] receives
+ *                     logp of the final states.  No atomics; chains do not interact; the outputs are bitwise reproducible and
+ *                     do not depend on how a run is cut into calls (step_offset advanced).  keep_every >= 1; steps,
+ *                     step_offset, keep_from, keep_every <= 2^40.                                                          */
+int mf_mala_ment_steps(float* x, int64_t chains, int d, int nslot, const float* desc, const int32_t* meta, const float* tables,
+                       int64_t table_floats, int prior_kind, float prior_a, float prior_lognorm, const float* noise,
+                       int64_t steps, int64_t step_offset, const float* scale, float drift_clip, int64_t keep_from,
+                       int64_t keep_every, float* out, int32_t* accepted, float* logp, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Differentiable log-density of classical MENT (no counterpart in the reference, whose interpolators are scipy on the host).
  * A purely additive entry point: MF_ABI_VERSION stays 5.  Slot arguments (nslot .. prior_lognorm) and limits exactly as
  * mf_ment_prob takes them; n = 0 and nslot = 0 are valid.

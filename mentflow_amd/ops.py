@@ -632,6 +632,42 @@ def ment_integrate(minv: torch.Tensor, coords: List[torch.Tensor], meas_axes, de
     return pred
 
 
+def _check_chain_steps(name: str, x, desc, meta, tables, noise, scale, accepted, step_offset, keep_from, keep_every, out,
+                       extra=()) -> Tuple[int, int, int, int, int, int]:
+    """The argument checks that mcmc_ment_steps and mala_ment_steps share; `name` opens the messages.  Returns
+    (chains, d, steps, step_offset, keep_from, keep_every)."""
+    if x.dim() != 2 or not 1 <= x.shape[1] <= 8:
+        raise RuntimeError(f"{name}: x[chains, d <= 8] expected (got {tuple(x.shape)})")
+    chains, d = x.shape
+    for what, t in (("x", x), ("noise", noise), ("scale", scale), ("tables", tables)):
+        if t.dtype != _F32:
+            raise RuntimeError(f"{name}: {what} must be float32 (got {t.dtype})")
+    if accepted.dtype != torch.int32 or tuple(accepted.shape) != (chains,):
+        raise RuntimeError(f"{name}: accepted must be int32[{chains}] (got {accepted.dtype}{tuple(accepted.shape)})")
+    if noise.dim() != 3 or tuple(noise.shape[1:]) != (d + 1, chains):
+        raise RuntimeError(f"{name}: noise[steps, {d + 1}, {chains}] expected (got {tuple(noise.shape)})")
+    if tuple(scale.shape) != (d,):
+        raise RuntimeError(f"{name}: scale[{d}] expected (got {tuple(scale.shape)})")
+    nslot = desc.shape[0]
+    if desc.dtype != _F32 or tuple(desc.shape) != (nslot, MENT_DESC) or meta.dtype != torch.int32 or tuple(meta.shape) != (nslot, 4):
+        raise RuntimeError(f"{name}: desc float32[nslot, {MENT_DESC}] and meta int32[nslot, 4] expected (got "
+                           f"{desc.dtype}{tuple(desc.shape)}, {meta.dtype}{tuple(meta.shape)})")
+    steps = noise.shape[0]
+    step_offset, keep_from, keep_every = int(step_offset), int(keep_from), int(keep_every)
+    if step_offset < 0 or keep_from < 0 or keep_every < 1:
+        raise RuntimeError(f"{name}: step_offset, keep_from >= 0 and keep_every >= 1 expected")
+    if out is not None:
+        last = step_offset + steps - 1 - keep_from                   # rows this call may write: those of steps g <= last
+        need = last // keep_every + 1 if last >= 0 else 0
+        if out.dtype != _F32 or out.dim() != 3 or tuple(out.shape[1:]) != (chains, d) or out.shape[0] < need:
+            raise RuntimeError(f"{name}: out[>= {need}, {chains}, {d}] float32 expected (got {out.dtype}"
+                               f"{tuple(out.shape)})")
+    for t in (noise, scale, accepted, out, desc, meta, tables, *extra):
+        if t is not None and t.device != x.device:
+            raise RuntimeError(f"{name}: all tensors must be on {x.device} (got one on {t.device})")
+    return chains, d, steps, step_offset, keep_from, keep_every
+
+
 def mcmc_ment_steps(x: torch.Tensor, desc: torch.Tensor, meta: torch.Tensor, tables: torch.Tensor, prior, noise: torch.Tensor,
                     scale: torch.Tensor, accepted: torch.Tensor, step_offset: int = 0, keep_from: int = 0, keep_every: int = 1,
                     out: Optional[torch.Tensor] = None) -> None:
@@ -639,38 +675,31 @@ def mcmc_ment_steps(x: torch.Tensor, desc: torch.Tensor, meta: torch.Tensor, tab
     (mf_mcmc_ment_steps, include/mentflow_hip.h).  noise[steps, d + 1, chains]: normal proposal rows and a uniform last row;
     scale[d] on the device; accepted[chains] int32 is added to; out[n_keep, chains, d] (or None) receives the state after every
     step g = step_offset + t with g >= keep_from and (g - keep_from) % keep_every == 0."""
-    if x.dim() != 2 or not 1 <= x.shape[1] <= 8:
-        raise RuntimeError(f"mcmc_ment_steps: x[chains, d <= 8] expected (got {tuple(x.shape)})")
-    chains, d = x.shape
-    for name, t in (("x", x), ("noise", noise), ("scale", scale), ("tables", tables)):
-        if t.dtype != _F32:
-            raise RuntimeError(f"mcmc_ment_steps: {name} must be float32 (got {t.dtype})")
-    if accepted.dtype != torch.int32 or tuple(accepted.shape) != (chains,):
-        raise RuntimeError(f"mcmc_ment_steps: accepted must be int32[{chains}] (got {accepted.dtype}{tuple(accepted.shape)})")
-    if noise.dim() != 3 or tuple(noise.shape[1:]) != (d + 1, chains):
-        raise RuntimeError(f"mcmc_ment_steps: noise[steps, {d + 1}, {chains}] expected (got {tuple(noise.shape)})")
-    if tuple(scale.shape) != (d,):
-        raise RuntimeError(f"mcmc_ment_steps: scale[{d}] expected (got {tuple(scale.shape)})")
-    nslot = desc.shape[0]
-    if desc.dtype != _F32 or tuple(desc.shape) != (nslot, MENT_DESC) or meta.dtype != torch.int32 or tuple(meta.shape) != (nslot, 4):
-        raise RuntimeError(f"mcmc_ment_steps: desc float32[nslot, {MENT_DESC}] and meta int32[nslot, 4] expected (got "
-                           f"{desc.dtype}{tuple(desc.shape)}, {meta.dtype}{tuple(meta.shape)})")
-    steps = noise.shape[0]
-    step_offset, keep_from, keep_every = int(step_offset), int(keep_from), int(keep_every)
-    if step_offset < 0 or keep_from < 0 or keep_every < 1:
-        raise RuntimeError("mcmc_ment_steps: step_offset, keep_from >= 0 and keep_every >= 1 expected")
-    if out is not None:
-        last = step_offset + steps - 1 - keep_from                   # rows this call may write: those of steps g <= last
-        need = last // keep_every + 1 if last >= 0 else 0
-        if out.dtype != _F32 or out.dim() != 3 or tuple(out.shape[1:]) != (chains, d) or out.shape[0] < need:
-            raise RuntimeError(f"mcmc_ment_steps: out[>= {need}, {chains}, {d}] float32 expected (got {out.dtype}"
-                               f"{tuple(out.shape)})")
-    for t in (noise, scale, accepted, out, desc, meta, tables):
-        if t is not None and t.device != x.device:
-            raise RuntimeError(f"mcmc_ment_steps: all tensors must be on {x.device} (got one on {t.device})")
+    chains, d, steps, step_offset, keep_from, keep_every = _check_chain_steps(
+        "mcmc_ment_steps", x, desc, meta, tables, noise, scale, accepted, step_offset, keep_from, keep_every, out)
     call("mf_mcmc_ment_steps", ptr(x), chains, d, desc.shape[0], ptr(desc), ptr(meta), ptr(tables), tables.numel(),
          int(prior[0]), float(prior[1]), float(prior[2]), ptr(noise), steps, step_offset, ptr(scale), keep_from, keep_every,
          ptr(out), ptr(accepted), stream_ptr(x))
+
+
+def mala_ment_steps(x: torch.Tensor, desc: torch.Tensor, meta: torch.Tensor, tables: torch.Tensor, prior, noise: torch.Tensor,
+                    scale: torch.Tensor, accepted: torch.Tensor, drift_clip: float = 1.0, step_offset: int = 0,
+                    keep_from: int = 0, keep_every: int = 1, out: Optional[torch.Tensor] = None,
+                    logp: Optional[torch.Tensor] = None) -> None:
+    """Advance the Metropolis-adjusted Langevin chains x[chains, d] IN PLACE by noise.shape[0] steps on the MENT density of the
+    slots (mf_mala_ment_steps, include/mentflow_hip.h).  Arguments as mcmc_ment_steps takes them, plus drift_clip >= 0 (the drift
+    is truncated to that many proposal standard deviations per axis) and logp[chains] float32 (or None), which receives the
+    log-density of the final states."""
+    chains, d, steps, step_offset, keep_from, keep_every = _check_chain_steps(
+        "mala_ment_steps", x, desc, meta, tables, noise, scale, accepted, step_offset, keep_from, keep_every, out, extra=(logp,))
+    drift_clip = float(drift_clip)
+    if not drift_clip >= 0.0:
+        raise RuntimeError(f"mala_ment_steps: drift_clip >= 0 expected (got {drift_clip})")
+    if logp is not None and (logp.dtype != _F32 or tuple(logp.shape) != (chains,)):
+        raise RuntimeError(f"mala_ment_steps: logp must be float32[{chains}] (got {logp.dtype}{tuple(logp.shape)})")
+    call("mf_mala_ment_steps", ptr(x), chains, d, desc.shape[0], ptr(desc), ptr(meta), ptr(tables), tables.numel(),
+         int(prior[0]), float(prior[1]), float(prior[2]), ptr(noise), steps, step_offset, ptr(scale), drift_clip, keep_from,
+         keep_every, ptr(out), ptr(accepted), ptr(logp), stream_ptr(x))
 
 
 def ment_logprob(x: torch.Tensor, desc: torch.Tensor, meta: torch.Tensor, tables: torch.Tensor, prior=(0, 0.0, 0.0),

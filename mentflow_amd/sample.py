@@ -14,7 +14,9 @@ Quirk kept from the reference: with ``noise`` truthy every axis also gets ``0.5 
 
 ``MetropolisHastingsSampler`` (no counterpart in the reference) draws particles from many independent random-walk
 Metropolis-Hastings chains instead: it needs point evaluations of the density only, so its cost does not grow as res^ndim.
-Same call contract as ``GridSampler``; kernel in mentflow_amd/csrc/mcmc.hip.
+Same call contract as ``GridSampler``; kernel in mentflow_amd/csrc/mcmc.hip.  ``LangevinSampler`` (no counterpart either) pushes
+those proposals along the gradient of the log-density and tests acceptance on logarithms (Metropolis-adjusted Langevin; kernel in
+mentflow_amd/csrc/mala.hip).  Both derive from ``_ChainSampler``, which holds everything but the transition.
 """
 from __future__ import annotations
 
@@ -117,36 +119,29 @@ log = logging.getLogger("mentflow_amd.sample")
 _NOISE_CHUNK_BYTES = 256 << 20      # noise of one launch of the fused path (generated per chunk, never for the whole run)
 
 
-class MetropolisHastingsSampler:
-    """`chains` independent random-walk Metropolis-Hastings chains on a density given by point evaluations.
+class _ChainSampler:
+    """What the particle samplers built on many independent Markov chains share: the constructor arguments, the persistent
+    chain states, the noise ([steps, ndim + 1, chains]: normal proposal rows and a uniform last row, drawn on the device in chunks
+    of _NOISE_CHUNK_BYTES), the bookkeeping of kept states and acceptance, and the call contract of ``GridSampler``.  A subclass
+    gives the transition: ``_fused_steps`` (its kernel), ``_generic_steps`` (the same rule in torch ops) and ``_target`` (what the
+    generic path evaluates)."""
 
-    One step of a chain at x with density p: y = x + step * z (z standard normal per axis), p_new = prob(y), u uniform on
-    [0, 1); accept iff ``p_new > 0 ? u * p < p_new : (p_new == 0 and p == 0)``.  Inside the support that is the Metropolis rule;
-    a chain outside it (p == 0) random-walks until it finds it and never leaves it again; a NaN p_new is rejected.  The noise
-    is ``torch.randn`` / ``torch.rand`` on the device, so ``torch.manual_seed`` fixes a run.
+    _generic_note = ""             # how the generic path differs, for the log line
 
-    Called with ``MENT.prob`` itself of a MENT whose slots all run through the kernels, the steps run in the fused kernel
-    (state and density in registers, one launch per chunk of steps); any other callable (``log_prob`` is NOT a density, a
-    subclass's override, a user function) takes the same rule in torch ops with one ``prob_func`` call per step, logged once.
-
-    ``sampler(prob_func, size)`` runs ``burn + ceil(size / chains) * thin`` steps, keeps every ``thin``-th state after the burn-in
-    and returns the first ``size`` rows of the kept block (step-major).  With ``persistent`` later calls continue from the stored
-    states and burn only ``burn_persistent`` (default ``thin``) steps: between Gauss-Seidel sub-steps the density moves little.
-    """
-
-    def __init__(self, ndim: int, chains: int = 65536, step: Union[float, Sequence[float]] = 0.25, burn: int = 200,
-                 thin: int = 10, start: Optional[torch.Tensor] = None, start_scale: float = 1.0, persistent: bool = True,
-                 burn_persistent: Optional[int] = None, device: torch.device = None) -> None:
+    def __init__(self, ndim: int, chains: int, step: Union[float, Sequence[float]], burn: int, thin: int,
+                 start: Optional[torch.Tensor], start_scale: float, persistent: bool, burn_persistent: Optional[int],
+                 device: torch.device) -> None:
+        name = type(self).__name__
         self.ndim, self.chains = int(ndim), int(chains)
         if not 1 <= self.ndim <= 8:
-            raise ValueError(f"MetropolisHastingsSampler: 1 <= ndim <= 8 expected (got {ndim})")
+            raise ValueError(f"{name}: 1 <= ndim <= 8 expected (got {ndim})")
         if self.chains < 1 or int(burn) < 0 or int(thin) < 1:
-            raise ValueError("MetropolisHastingsSampler: chains >= 1, burn >= 0 and thin >= 1 expected")
+            raise ValueError(f"{name}: chains >= 1, burn >= 0 and thin >= 1 expected")
         self.step = [float(step)] * self.ndim if isinstance(step, (int, float)) else [float(v) for v in step]
         if len(self.step) != self.ndim:
-            raise ValueError(f"MetropolisHastingsSampler: step must be a float or {self.ndim} per-axis scales (got {len(self.step)})")
+            raise ValueError(f"{name}: step must be a float or {self.ndim} per-axis scales (got {len(self.step)})")
         if start is not None and tuple(start.shape) != (self.chains, self.ndim):
-            raise ValueError(f"MetropolisHastingsSampler: start[{self.chains}, {self.ndim}] expected (got {tuple(start.shape)})")
+            raise ValueError(f"{name}: start[{self.chains}, {self.ndim}] expected (got {tuple(start.shape)})")
         self.burn, self.thin = int(burn), int(thin)
         self.start, self.start_scale = start, float(start_scale)
         self.persistent = bool(persistent)
@@ -174,7 +169,7 @@ class MetropolisHastingsSampler:
         owner = getattr(prob_func, "__self__", None)
         if isinstance(owner, MENT) and getattr(prob_func, "__func__", None) is MENT.prob:
             if owner.ndim != self.ndim:
-                raise ValueError(f"MetropolisHastingsSampler(ndim={self.ndim}) called with the density of a MENT of ndim={owner.ndim}")
+                raise ValueError(f"{type(self).__name__}(ndim={self.ndim}) called with the density of a MENT of ndim={owner.ndim}")
             return owner.fused_args()
         return None
 
@@ -194,6 +189,94 @@ class MetropolisHastingsSampler:
         nz[:, self.ndim].uniform_()
         return nz
 
+    def _target(self, prob_func: Callable, fused) -> Optional[Callable]:
+        """What `_generic_steps` evaluates when `fused` (the kernel's arguments) is None."""
+        return prob_func
+
+    def _fused_steps(self, x, args, noise, scale, accepted, t0, keep_from, keep_every, out) -> None:
+        raise NotImplementedError
+
+    def _generic_steps(self, target, noise, scale, accepted, t0, keep_from, keep_every, out) -> None:
+        raise NotImplementedError
+
+    def run(self, prob_func: Callable, steps: int, noise: Optional[torch.Tensor] = None, keep_from: int = 0,
+            keep_every: int = 1) -> torch.Tensor:
+        """Advance every chain by `steps` steps and return the states after the steps g >= keep_from with
+        (g - keep_from) % keep_every == 0 as [n_keep, chains, ndim].  noise: [steps, ndim + 1, chains] (normal proposal rows,
+        a uniform last row), default drawn on the device in chunks."""
+        name = type(self).__name__
+        steps, keep_from, keep_every = int(steps), int(keep_from), int(keep_every)
+        if steps < 0 or keep_from < 0 or keep_every < 1:
+            raise ValueError(f"{name}.run: steps, keep_from >= 0 and keep_every >= 1 expected")
+        args = self._fused_args(prob_func)
+        target = self._target(prob_func, args)
+        if self.state is None:
+            self._init_state(prob_func)
+        x = self.state
+        _lib.ptr(x)                                            # the usual refusal of tensors the library does not compute on
+        if noise is not None:
+            if tuple(noise.shape) != (steps, self.ndim + 1, self.chains):
+                raise ValueError(f"{name}.run: noise[{steps}, {self.ndim + 1}, {self.chains}] expected "
+                                 f"(got {tuple(noise.shape)})")
+            noise = noise.to(x.device, torch.float32).contiguous()
+        if args is None and not self._logged_generic:
+            self._logged_generic = True
+            log.info("%s: %s is not the bound MENT.prob of a fully fused MENT: the generic path runs (the "
+                     "same transition rule in torch ops, %s)", name, getattr(prob_func, "__qualname__", prob_func),
+                     self._generic_note)
+        n_keep = 0 if steps <= keep_from else (steps - 1 - keep_from) // keep_every + 1
+        out = torch.empty(n_keep, self.chains, self.ndim, device=x.device) if n_keep else None
+        accepted = torch.zeros(self.chains, dtype=torch.int32, device=x.device)
+        scale = torch.tensor(self.step, dtype=torch.float32, device=x.device)
+        per = max(1, _NOISE_CHUNK_BYTES // (4 * (self.ndim + 1) * self.chains))
+        for t0 in range(0, steps, per):
+            t1 = min(steps, t0 + per)
+            nz = noise[t0:t1] if noise is not None else self._noise(t1 - t0, x.device)
+            if args is not None:
+                self._fused_steps(x, args, nz, scale, accepted, t0, keep_from, keep_every, out)
+            else:
+                self._generic_steps(target, nz, scale, accepted, t0, keep_from, keep_every, out)
+        self.acceptance = accepted.sum().to(torch.float32) / float(max(1, steps) * self.chains)
+        return out if out is not None else torch.empty(0, self.chains, self.ndim, device=x.device)
+
+    def __call__(self, prob_func: Callable, size: int) -> torch.Tensor:
+        size = int(size)
+        if not self.persistent:
+            self.reset()
+        burn = self.burn if self.state is None else self.burn_persistent
+        rounds = max(1, math.ceil(size / self.chains))
+        kept = self.run(prob_func, burn + rounds * self.thin, keep_from=burn + self.thin - 1, keep_every=self.thin)
+        return kept.reshape(-1, self.ndim)[:size]
+
+
+class MetropolisHastingsSampler(_ChainSampler):
+    """`chains` independent random-walk Metropolis-Hastings chains on a density given by point evaluations.
+
+    One step of a chain at x with density p: y = x + step * z (z standard normal per axis), p_new = prob(y), u uniform on
+    [0, 1); accept iff ``p_new > 0 ? u * p < p_new : (p_new == 0 and p == 0)``.  Inside the support that is the Metropolis rule;
+    a chain outside it (p == 0) random-walks until it finds it and never leaves it again; a NaN p_new is rejected.  The noise
+    is ``torch.randn`` / ``torch.rand`` on the device, so ``torch.manual_seed`` fixes a run.
+
+    Called with ``MENT.prob`` itself of a MENT whose slots all run through the kernels, the steps run in the fused kernel
+    (state and density in registers, one launch per chunk of steps); any other callable (``log_prob`` is NOT a density, a
+    subclass's override, a user function) takes the same rule in torch ops with one ``prob_func`` call per step, logged once.
+
+    ``sampler(prob_func, size)`` runs ``burn + ceil(size / chains) * thin`` steps, keeps every ``thin``-th state after the burn-in
+    and returns the first ``size`` rows of the kept block (step-major).  With ``persistent`` later calls continue from the stored
+    states and burn only ``burn_persistent`` (default ``thin``) steps: between Gauss-Seidel sub-steps the density moves little.
+    """
+
+    _generic_note = "one density call per step"
+
+    def __init__(self, ndim: int, chains: int = 65536, step: Union[float, Sequence[float]] = 0.25, burn: int = 200,
+                 thin: int = 10, start: Optional[torch.Tensor] = None, start_scale: float = 1.0, persistent: bool = True,
+                 burn_persistent: Optional[int] = None, device: torch.device = None) -> None:
+        super().__init__(ndim, chains, step, burn, thin, start, start_scale, persistent, burn_persistent, device)
+
+    def _fused_steps(self, x, args, noise, scale, accepted, t0, keep_from, keep_every, out) -> None:
+        ops.mcmc_ment_steps(x, args[0], args[1], args[2], args[3], noise, scale, accepted, step_offset=t0,
+                            keep_from=keep_from, keep_every=keep_every, out=out)
+
     def _generic_steps(self, prob_func, noise, scale, accepted, t0, keep_from, keep_every, out) -> None:
         x, d = self.state, self.ndim
         p = prob_func(x)
@@ -210,49 +293,99 @@ class MetropolisHastingsSampler:
                 out[k // keep_every] = x
         self.state = x.contiguous()
 
-    def run(self, prob_func: Callable, steps: int, noise: Optional[torch.Tensor] = None, keep_from: int = 0,
-            keep_every: int = 1) -> torch.Tensor:
-        """Advance every chain by `steps` steps and return the states after the steps g >= keep_from with
-        (g - keep_from) % keep_every == 0 as [n_keep, chains, ndim].  noise: [steps, ndim + 1, chains] (normal proposal rows,
-        a uniform last row), default drawn on the device in chunks."""
-        steps, keep_from, keep_every = int(steps), int(keep_from), int(keep_every)
-        if steps < 0 or keep_from < 0 or keep_every < 1:
-            raise ValueError("MetropolisHastingsSampler.run: steps, keep_from >= 0 and keep_every >= 1 expected")
-        args = self._fused_args(prob_func)
-        if self.state is None:
-            self._init_state(prob_func)
-        x = self.state
-        _lib.ptr(x)                                            # the usual refusal of tensors the library does not compute on
-        if noise is not None:
-            if tuple(noise.shape) != (steps, self.ndim + 1, self.chains):
-                raise ValueError(f"MetropolisHastingsSampler.run: noise[{steps}, {self.ndim + 1}, {self.chains}] expected "
-                                 f"(got {tuple(noise.shape)})")
-            noise = noise.to(x.device, torch.float32).contiguous()
-        if args is None and not self._logged_generic:
-            self._logged_generic = True
-            log.info("MetropolisHastingsSampler: %s is not the bound MENT.prob of a fully fused MENT: the generic path runs (the "
-                     "same transition rule in torch ops, one density call per step)", getattr(prob_func, "__qualname__", prob_func))
-        n_keep = 0 if steps <= keep_from else (steps - 1 - keep_from) // keep_every + 1
-        out = torch.empty(n_keep, self.chains, self.ndim, device=x.device) if n_keep else None
-        accepted = torch.zeros(self.chains, dtype=torch.int32, device=x.device)
-        scale = torch.tensor(self.step, dtype=torch.float32, device=x.device)
-        per = max(1, _NOISE_CHUNK_BYTES // (4 * (self.ndim + 1) * self.chains))
-        for t0 in range(0, steps, per):
-            t1 = min(steps, t0 + per)
-            nz = noise[t0:t1] if noise is not None else self._noise(t1 - t0, x.device)
-            if args is not None:
-                ops.mcmc_ment_steps(x, args[0], args[1], args[2], args[3], nz, scale, accepted, step_offset=t0,
-                                    keep_from=keep_from, keep_every=keep_every, out=out)
-            else:
-                self._generic_steps(prob_func, nz, scale, accepted, t0, keep_from, keep_every, out)
-        self.acceptance = accepted.sum().to(torch.float32) / float(max(1, steps) * self.chains)
-        return out if out is not None else torch.empty(0, self.chains, self.ndim, device=x.device)
 
-    def __call__(self, prob_func: Callable, size: int) -> torch.Tensor:
-        size = int(size)
-        if not self.persistent:
-            self.reset()
-        burn = self.burn if self.state is None else self.burn_persistent
-        rounds = max(1, math.ceil(size / self.chains))
-        kept = self.run(prob_func, burn + rounds * self.thin, keep_from=burn + self.thin - 1, keep_every=self.thin)
-        return kept.reshape(-1, self.ndim)[:size]
+class LangevinSampler(_ChainSampler):
+    """`chains` independent Metropolis-adjusted Langevin chains: the proposals of ``MetropolisHastingsSampler`` pushed along the
+    gradient of the log-density, and the acceptance test made on logarithms.
+
+    One step of a chain at x with l = log p(x), g = grad log p(x) and s = step per axis: drift(x) = clamp(s^2 g / 2, -drift_clip
+    s, drift_clip s) per axis, y = x + drift(x) + s z, r = (x - y - drift(y)) / s, D = l(y) - l + (|z|^2 - |r|^2) / 2; accept iff
+    ``l(y) > -inf ? (l == -inf or log u < D) : (l(y) == -inf and l == -inf)``, and never with a NaN in l(y), z or u.  The
+    truncated drift is a function of the state alone, so the Metropolis correction is exact; ``drift_clip`` bounds it in proposal
+    standard deviations (h' / h is unbounded next to a zero of a Lagrange function), 0 gives a driftless walk.  The conventions
+    are those of the random-walk sampler: a chain inside the support never leaves it, a chain outside it (no drift there)
+    random-walks until it finds it.  Because sums of logarithms are compared, the rule holds where the fp32 product of a hundred
+    factors has underflowed and the random-walk sampler sees no support at all.
+
+    Called with ``MENT.prob`` itself of a MENT whose slots all run through the kernels, the steps run in the fused kernel
+    (mentflow_amd/csrc/mala.hip: state, log-density and gradient in registers).  Otherwise the same rule runs in torch ops, logged
+    once, on ``log_density`` if given, else on ``MENT.log_density`` of the MENT that ``prob_func`` is bound to, with the gradient
+    from autograd; without either a ``ValueError`` says so.  Call contract, persistence and noise as ``MetropolisHastingsSampler``.
+    """
+
+    _generic_note = "one log-density call and one backward pass per step"
+
+    def __init__(self, ndim: int, chains: int = 65536, step: Union[float, Sequence[float]] = 0.25, burn: int = 200,
+                 thin: int = 10, start: Optional[torch.Tensor] = None, start_scale: float = 1.0, persistent: bool = True,
+                 burn_persistent: Optional[int] = None, device: torch.device = None, drift_clip: float = 1.0,
+                 log_density: Optional[Callable] = None) -> None:
+        super().__init__(ndim, chains, step, burn, thin, start, start_scale, persistent, burn_persistent, device)
+        if not all(v > 0 for v in self.step):
+            raise ValueError(f"LangevinSampler: step > 0 expected on every axis (got {self.step})")
+        self.drift_clip = float(drift_clip)
+        if not self.drift_clip >= 0.0:
+            raise ValueError(f"LangevinSampler: drift_clip >= 0 expected (got {drift_clip})")
+        self.log_density = log_density
+
+    def _target(self, prob_func: Callable, fused) -> Optional[Callable]:
+        from .ment import MENT
+        if fused is not None:
+            return None
+        if self.log_density is not None:
+            return self.log_density
+        owner = getattr(prob_func, "__self__", None)
+        if isinstance(owner, MENT) and getattr(prob_func, "__func__", None) is type(owner).prob:
+            # a subclass that overrides prob alone has a density that MENT.log_density does not describe
+            if type(owner).prob is MENT.prob or type(owner).log_density is not MENT.log_density:
+                if owner.ndim != self.ndim:
+                    raise ValueError(f"LangevinSampler(ndim={self.ndim}) called with the density of a MENT of ndim={owner.ndim}")
+                return owner.log_density
+        raise ValueError("LangevinSampler needs a differentiable log-density: pass log_density=..., or call it with the bound "
+                         f"prob of a MENT (got {getattr(prob_func, '__qualname__', prob_func)})")
+
+    def _fused_steps(self, x, args, noise, scale, accepted, t0, keep_from, keep_every, out) -> None:
+        ops.mala_ment_steps(x, args[0], args[1], args[2], args[3], noise, scale, accepted, drift_clip=self.drift_clip,
+                            step_offset=t0, keep_from=keep_from, keep_every=keep_every, out=out)
+
+    @staticmethod
+    def _value_and_grad(log_density: Callable, x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(l, grad l) at x with the kernel's conventions: the gradient row of a point outside the support is 0, that of a NaN
+        point NaN."""
+        x = x.detach().requires_grad_(True)
+        with torch.enable_grad():
+            lp = log_density(x)
+            if not lp.requires_grad:
+                raise ValueError("LangevinSampler needs a differentiable log-density: the one it was given returned a tensor that "
+                                 "does not depend on x through autograd")
+            (g,) = torch.autograd.grad(lp.sum(), x)
+        lp = lp.detach()
+        g = torch.where(torch.isneginf(lp)[:, None], torch.zeros_like(g), g)
+        return lp, torch.where(torch.isnan(lp)[:, None], torch.full_like(g, float("nan")), g)
+
+    def _generic_steps(self, log_density, noise, scale, accepted, t0, keep_from, keep_every, out) -> None:
+        x, d = self.state, self.ndim
+        a, c = (0.5 * scale) * scale, torch.tensor(self.drift_clip, dtype=torch.float32, device=x.device) * scale
+
+        def drift(g):
+            return torch.minimum(torch.maximum(a * g, -c), c)
+
+        lp, g = self._value_and_grad(log_density, x)
+        for t in range(noise.shape[0]):
+            z, u = noise[t, :d].T, noise[t, d]
+            # the kernel's fma(scale, z, x + drift): the fp32 product is exact in fp64, so a double rounding at most apart
+            y = ((x + drift(g)).double() + z.double() * scale.double()).float()
+            lp_new, g_new = self._value_and_grad(log_density, y)
+            r = ((x - y) - drift(g_new)) / scale
+            zz = (z * z).sum(1)
+            delta = (lp_new - lp) + 0.5 * (zz - (r * r).sum(1))
+            outside = torch.isneginf(lp)
+            accept = torch.where(lp_new > float("-inf"), outside | (torch.log(u) < delta), torch.isneginf(lp_new) & outside)
+            accept = accept & ~torch.isnan(u) & ~torch.isnan(zz)
+            x = torch.where(accept[:, None], y, x)
+            g = torch.where(accept[:, None], g_new, g)
+            lp = torch.where(accept, lp_new, lp)
+            accepted += accept.to(torch.int32)
+            k = t0 + t - keep_from
+            if out is not None and k >= 0 and k % keep_every == 0:
+                out[k // keep_every] = x
+        self.state = x.contiguous()
