@@ -384,6 +384,38 @@ int mf_ment_logprob(const float* x, int64_t n, int d, int nslot, const float* de
                     void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Gradient of the log-density of classical MENT with respect to its Lagrange tables: the adjoint of mf_ment_logprob in
+ * `tables` (no counterpart in the reference).  A purely additive entry point: MF_ABI_VERSION stays 5.  x, n, d and the slot
+ * arguments (nslot .. table_floats) and their limits exactly as mf_ment_logprob takes them (the prior does not depend on the
+ * tables and is not passed); n = 0 zeroes the outputs and returns 0.
+ *
+ * mf_ment_logprob_tables_bwd:  grad_log[e] = sum_i weight[i] rho_e(x_i) = dL / d log tables[e] for L = sum_i weight[i] logp[i],
+ *                  grad_tab[e] (may be NULL) = grad_log[e] / tables[e] = dL / d tables[e] where tables[e] > 0, else 0: a zero
+ *                  entry is outside MENT's support and stays there, as under the multiplicative update (the one-sided
+ *                  derivative there is not returned).  logp[n] is what mf_ment_logprob returned for the same arguments, weight[n]
+ *                  the upstream dL / dlogp.  A row takes part iff logp[i] is finite and weight[i] != 0; a row with logp = -inf
+ *                  contributes nothing whatever its weight (NaN included).  Projections and cells (i, w) are those of
+ *                  mf_ment_logprob bit for bit.  Per slot and node e of the cell, rho_e = node weight * tables[e] / h clamped to
+ *                  [0, 1]: for a 1-D slot with h = a (1 - w) + b w the pair a (1 - w) / h, b w / h, for a 2-D slot the four
+ *                  bilinear terms; the clamp is a no-op up to rounding for non-negative tables, and for tables with negative
+ *                  entries the result is only promised finite.  A slot with h >= 1e10 (on the upper clamp: a constant)
+ *                  contributes nothing, nor does a slot with h <= 0 or NaN on a row the caller declared live.
+ *                  Fixed point: wmax is a DEVICE scalar >= 0, the maximum of |weight| over the rows with finite logp;
+ *                  P = 2^ceil(log2 wmax), F = min(50, 62 - ceil(log2 max(n, 2))); each contribution is
+ *                  round((weight / P) rho 2^F) (|weight| / P is clamped to 1 should wmax be too small), added as a signed
+ *                  64-bit integer in two's complement, which cannot overflow; acc[table_floats] is workspace the call zeroes
+ *                  first; a finishing pass writes acc * P * 2^-F, formed in fp64 and rounded once.  wmax == 0 gives all zeros.
+ *                  Integer atomics only (64-bit, in LDS while descriptors + tables fit the budget of mf_ment_logprob's
+ *                  tables-in-LDS instance, else straight into acc): bitwise reproducible, independent of the order of the rows.
+ *                  Poison: status[0] (DEVICE, int32) is set to 0 and then to non-zero if wmax is NaN or inf, if a row has NaN
+ *                  logp and weight != 0 (NaN counts), or if a row has finite logp and a non-finite weight; such rows add
+ *                  nothing, the outputs stay finite, and the caller decides (ops.ment_logprob_table_grad returns NaN). */
+int mf_ment_logprob_tables_bwd(const float* x, int64_t n, int d, int nslot, const float* desc, const int32_t* meta,
+                               const float* tables, int64_t table_floats, const float* logp, const float* weight,
+                               const float* wmax, unsigned long long* acc, float* grad_log, float* grad_tab, int32_t* status,
+                               void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Sliced Wasserstein distance  (mentflow/loss.py:20-42, where the 1-D transport cost is POT's ot.lp.wasserstein_1d on the
  * host).  Purely additive entry points: MF_ABI_VERSION stays 5.  No float atomics, fp64 sums in a fixed order: every output
  * is bitwise reproducible.  All sizes obey P * n < 2^31.

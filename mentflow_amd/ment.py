@@ -363,17 +363,23 @@ class MENT:
         return torch.log(self.prob(x) + pad)
 
     def log_density(self, x: torch.Tensor, pad: float = 0.0) -> torch.Tensor:
-        """log of the (unnormalised) density of ``prob``, differentiable in x: the sum over all slots of log clamp(h, 0, 1e10)
-        plus ``prior.log_prob(x)``, from ops.MentLogProbFn per pre-transform chain (autograd runs through the chain's
-        pre-transforms) and, for the slots outside the chains, from the same kernel on their projected coordinates or from
-        ``_interp_torch`` when their centres are not uniform.
+        """log of the (unnormalised) density of ``prob``, differentiable in x and in the Lagrange tables
+        (``lagrange_functions[i][j].values``): the sum over all slots of log clamp(h, 0, 1e10) plus ``prior.log_prob(x)``, from
+        ops.MentLogProbFn per pre-transform chain (autograd runs through the chain's pre-transforms) and, for the slots outside
+        the chains, from the same kernel on their projected coordinates or from ``_interp_torch`` when their centres are not
+        uniform.
 
         Where ``log_prob`` is log(prob + pad) of an fp32 product — the constant log(pad) once a hundred factors have
         underflowed — this sums logarithms: finite and accurate wherever every factor is positive.  Outside the support the
         value is -inf and the gradient row 0 (nothing pulls such a point); a NaN coordinate gives NaN in both.  The derivative
         is that of the cell which holds the point: the right derivative at an interior bin centre, the left one at the last
-        centre.  The Lagrange functions are constants here.  ``pad > 0`` returns logaddexp(log_density, log pad), which is
-        log(prob + pad) wherever that is representable.  No host synchronisation: the call can be captured in a graph."""
+        centre.  A table whose ``values`` require a gradient receives d / d values[e] = sum_n g_n rho_e(x_n) / values[e], the
+        weighted histogram of the responsibilities rho (the share of the interpolant h that node e carries at the point, in
+        [0, 1]) divided by the table; an entry that is not positive receives 0 (it is outside MENT's support and stays there, as
+        under ``gauss_seidel_update``), a factor on the upper clamp is a constant, and rows outside the support pass nothing.
+        That makes the MENT dual log Z(exp lambda) - sum g_hat Delta lambda an ordinary autograd objective in lambda = log
+        values (examples/fit_ment_dual.py).  ``pad > 0`` returns logaddexp(log_density, log pad), which is log(prob + pad)
+        wherever that is representable.  No host synchronisation: the call, and its backward, can be captured in a graph."""
         chains, torch_slots = self._get_plan()
         x = x.to(torch.float32)
         prior = _prior_args(self.prior)
@@ -407,6 +413,36 @@ class MENT:
         if pad > 0.0:
             total = torch.logaddexp(total, torch.full_like(total, math.log(pad)))
         return total
+
+    def table_responsibilities(self, x: torch.Tensor, weights: Optional[torch.Tensor] = None) -> List[List[torch.Tensor]]:
+        """sum_n w_n rho(x_n) per slot, in the shape of each table: rho is the share of the slot's interpolant that a node of
+        the cell holding the point carries (1-D: a (1 - w) / h and b w / h; they sum to 1 per slot and point), so each result
+        is the w-weighted soft histogram of the batch on the slot's centres.  ``weights`` [len(x)] defaults to 1 / len(x);
+        rows outside the support contribute nothing.  This is the model-side term of the gradient of the MENT dual in the
+        log-tables, for every slot from one batch.  One code path for every kind of slot: autograd of ``log_density`` on
+        leaf copies of the tables, multiplied by the tables."""
+        x = x.to(torch.float32)
+        if weights is None:
+            weights = torch.full((x.shape[0],), 1.0 / max(x.shape[0], 1), dtype=torch.float32, device=x.device)
+        functions = [lf for group in self.lagrange_functions for lf in group]
+        kept = [lf.values for lf in functions]
+        leaves = [v.detach().to(torch.float32).clone().requires_grad_(True) for v in kept]
+        try:
+            for lf, leaf in zip(functions, leaves):
+                lf.values = leaf
+            with torch.enable_grad():
+                lp = self.log_density(x.detach())
+                total = (torch.where(torch.isneginf(lp), torch.zeros_like(lp), lp) * weights.to(lp.device, torch.float32)).sum()
+                grads = torch.autograd.grad(total, leaves, allow_unused=True) if leaves else []
+        finally:
+            for lf, v in zip(functions, kept):
+                lf.values = v
+        flat = [torch.zeros_like(leaf) if g is None else g * leaf.detach() for g, leaf in zip(grads, leaves)]
+        out, at = [], 0
+        for group in self.lagrange_functions:
+            out.append(flat[at:at + len(group)])
+            at += len(group)
+        return out
 
     def prob(self, x: torch.Tensor) -> torch.Tensor:
         chains, torch_slots = self._get_plan()

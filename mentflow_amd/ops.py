@@ -725,25 +725,73 @@ def ment_logprob(x: torch.Tensor, desc: torch.Tensor, meta: torch.Tensor, tables
     return logp, grad
 
 
+def ment_logprob_table_grad(x: torch.Tensor, desc: torch.Tensor, meta: torch.Tensor, tables: torch.Tensor, logp: torch.Tensor,
+                            weight: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(grad_log, grad_tab), both [tables.numel()], of mf_ment_logprob_tables_bwd (include/mentflow_hip.h): the gradient of
+    sum_n weight[n] logp[n] with respect to log tables (the weighted histogram of responsibilities) and to tables (that divided by
+    the table, 0 where the table is not positive).  logp[n] is what ment_logprob returned for the same x and slots, weight[n] the
+    upstream gradient; rows with logp = -inf are ignored whatever their weight.  A NaN logp with a non-zero weight, or a
+    non-finite weight on a row with finite logp, makes both results all NaN (decided on the device: no host synchronisation).
+    Integer accumulation: bitwise reproducible and independent of the order of the rows."""
+    if x.dim() != 2 or not 1 <= x.shape[1] <= 8:
+        raise RuntimeError(f"ment_logprob_table_grad: x[n, d <= 8] expected (got {tuple(x.shape)})")
+    x, tables, logp, weight = _f32c(x), _f32c(tables), _f32c(logp), _f32c(weight)
+    n, d = x.shape
+    nslot = desc.shape[0]
+    if desc.dtype != _F32 or tuple(desc.shape) != (nslot, MENT_DESC) or meta.dtype != torch.int32 or tuple(meta.shape) != (nslot, 4):
+        raise RuntimeError(f"ment_logprob_table_grad: desc float32[nslot, {MENT_DESC}] and meta int32[nslot, 4] expected (got "
+                           f"{desc.dtype}{tuple(desc.shape)}, {meta.dtype}{tuple(meta.shape)})")
+    if tuple(logp.shape) != (n,) or tuple(weight.shape) != (n,):
+        raise RuntimeError(f"ment_logprob_table_grad: logp[{n}] and weight[{n}] expected (got {tuple(logp.shape)}, "
+                           f"{tuple(weight.shape)})")
+    for t in (desc, meta, tables, logp, weight):
+        if t.device != x.device:
+            raise RuntimeError(f"ment_logprob_table_grad: all tensors must be on {x.device} (got one on {t.device})")
+    size = tables.numel()
+    if n > 0:
+        wmax = torch.where(torch.isfinite(logp), weight.abs(), torch.zeros_like(weight)).amax().reshape(1)
+    else:
+        wmax = torch.zeros(1, dtype=_F32, device=x.device)
+    acc = torch.empty(max(size, 1), dtype=torch.int64, device=x.device)
+    status = torch.empty(1, dtype=torch.int32, device=x.device)
+    grad_log = torch.empty(size, dtype=_F32, device=x.device)
+    grad_tab = torch.empty(size, dtype=_F32, device=x.device)
+    call("mf_ment_logprob_tables_bwd", ptr(x), n, d, nslot, ptr(desc), ptr(meta), ptr(tables), size, ptr(logp), ptr(weight),
+         ptr(wmax), ptr(acc), ptr(grad_log), ptr(grad_tab), ptr(status), stream_ptr(x))
+    bad = status != 0
+    nan = torch.full_like(grad_log, float("nan"))
+    return torch.where(bad, nan, grad_log), torch.where(bad, nan, grad_tab)
+
+
 class MentLogProbFn(torch.autograd.Function):
-    """x[n, d] -> logp[n] of ment_logprob, differentiable in x: one kernel launch computes the value and, when x needs a gradient,
-    d logp / dx, which the backward scales by the incoming gradient.  Rows with logp = -inf pass no gradient whatever comes in
-    (0 * inf would be NaN).  Tables, descriptors and the prior are constants; the backward is not differentiable again."""
+    """x[n, d] -> logp[n] of ment_logprob, differentiable in x and in tables: one kernel launch computes the value and, when x
+    needs a gradient, d logp / dx, which the backward scales by the incoming gradient.  Rows with logp = -inf pass no gradient
+    whatever comes in (0 * inf would be NaN).  When tables needs a gradient the backward launches ment_logprob_table_grad on the
+    saved x and logp: d / d tables[e] = sum_n g[n] rho_e(n) / tables[e], 0 where tables[e] <= 0.  Descriptors and the prior are
+    constants; the backward is not differentiable again."""
 
     @staticmethod
     def forward(ctx, x, desc, meta, tables, prior):
         want = bool(ctx.needs_input_grad[0])
+        ctx.want_tables = bool(ctx.needs_input_grad[3])
         logp, grad = ment_logprob(x, desc, meta, tables, prior, want_grad=want)
-        if want:
+        if ctx.want_tables:
+            ctx.save_for_backward(grad, logp, x, desc, meta, tables)
+        elif want:
             ctx.save_for_backward(grad, logp)
         return logp
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        grad, logp = ctx.saved_tensors
-        gx = torch.where(torch.isneginf(logp)[:, None], torch.zeros_like(grad), g[:, None] * grad)
-        return gx, None, None, None, None
+        grad, logp = ctx.saved_tensors[:2]
+        gx = gt = None
+        if grad is not None:
+            gx = torch.where(torch.isneginf(logp)[:, None], torch.zeros_like(grad), g[:, None] * grad)
+        if ctx.want_tables:
+            x, desc, meta, tables = ctx.saved_tensors[2:]
+            gt = ment_logprob_table_grad(x, desc, meta, tables, logp, g.contiguous())[1].reshape(tables.shape)
+        return gx, None, None, gt, None
 
 
 # ------------------------------------------------------------------------------------------------ sliced Wasserstein distance
