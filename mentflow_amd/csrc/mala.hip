@@ -21,18 +21,21 @@
 // l and g are recomputed from x at entry: nothing but x crosses launches, and tables that changed between calls are picked up.
 // Nothing in a chain depends on another chain or on how the steps are cut into launches (keeping is decided by the global step
 // index alone): outputs are bitwise reproducible and 40 steps in one launch equal 4 launches of 10.  No atomics.
+#include "ment_chain.h"
 #include "ment_logp_point.h"
 
 namespace mf {
 
+// The fields of ChainArgs plus logp and drift_clip, in the order the kernel was measured with: the order is the layout of the
+// kernel arguments, and with logp behind d the kernel measured 1.5-2 % slower (profiles/ment_refactor_ab.json).
 struct MalaArgs {
     const float* noise;     // [steps][d + 1][chains]
     const float* scale;     // [d] proposal scale per axis
     float* out;             // [n_keep][chains][d] or null
     float* logp;            // [chains] or null: logp of the final states
     int64_t steps;
-    int64_t keep_t;         // first step t of this launch that is kept (>= steps: none), formed on the host from step_offset,
-    int64_t keep_row;       // keep_from and keep_every, and the row of `out` it goes to
+    int64_t keep_t;         // as in ChainArgs
+    int64_t keep_row;
     int64_t keep_every;
     int chains;
     int d;
@@ -62,12 +65,12 @@ __global__ __launch_bounds__(MENT_BLOCK) void mala_ment_steps_kernel(float* __re
         xv[j] = (j < d) ? x[(int64_t)c * d + j] : 0.0f;
         sc[j] = (j < d) ? ma.scale[j] : 0.0f;
     }
-    float lp = logp_point<TAB_LDS, true>(xv, d, desc, meta, tab, sa, inv_a2, g);
+    float lp = logp_point<true>(xv, d, desc, meta, tab, sa, inv_a2, g);
     int acc = 0;
     const int64_t row = ma.chains;                     // floats per noise row
     int64_t keep_t = ma.keep_t, keep_row = ma.keep_row;
     for (int64_t t = 0; t < ma.steps; ++t) {
-        const float* nz = ma.noise + t * (d + 1) * row + c;
+        const float* nz = chain_noise(ma, t, c);
         float yv[MENT_DMAX], gy[MENT_DMAX];
         float zz = 0.0f;
 #pragma unroll
@@ -80,7 +83,7 @@ __global__ __launch_bounds__(MENT_BLOCK) void mala_ment_steps_kernel(float* __re
             }
         }
         const float u = nz[d * row];
-        const float lp_new = logp_point<TAB_LDS, true>(yv, d, desc, meta, tab, sa, inv_a2, gy);
+        const float lp_new = logp_point<true>(yv, d, desc, meta, tab, sa, inv_a2, gy);
         float rr = 0.0f;
 #pragma unroll
         for (int j = 0; j < MENT_DMAX; ++j) {
@@ -99,14 +102,7 @@ __global__ __launch_bounds__(MENT_BLOCK) void mala_ment_steps_kernel(float* __re
         }
         lp = accept ? lp_new : lp;
         acc += accept ? 1 : 0;
-        if (t == keep_t) {
-            float* o = ma.out + (keep_row * row + c) * d;
-#pragma unroll
-            for (int j = 0; j < MENT_DMAX; ++j)
-                if (j < d) o[j] = xv[j];
-            keep_t += ma.keep_every;
-            ++keep_row;
-        }
+        chain_keep(ma, t, c, xv, keep_t, keep_row);
     }
 #pragma unroll
     for (int j = 0; j < MENT_DMAX; ++j)
@@ -127,37 +123,15 @@ extern "C" int mf_mala_ment_steps(float* x, int64_t chains, int d, int nslot, co
     size_t smem;
     bool tl;
     if (slot_geometry(d, nslot, table_floats, prior_kind, &smem, &tl)) return 1;
-    if (chains < 0 || chains > 2147483647LL - MENT_BLOCK) return fail("mala: bad chain count %lld", (long long)chains);
-    if (steps < 0 || step_offset < 0 || keep_from < 0) return fail("mala: steps, step_offset and keep_from must be >= 0");
-    if (keep_every < 1) return fail("mala: keep_every must be >= 1 (got %lld)", (long long)keep_every);
-    const int64_t lim = (int64_t)1 << 40;              // keeps the step arithmetic far from overflow
-    if (steps > lim || step_offset > lim || keep_from > lim || keep_every > lim) return fail("mala: step counts beyond 2^40");
+    MalaArgs ma;
+    if (chain_args("mala", chains, d, noise, steps, step_offset, scale, keep_from, keep_every, out, &ma)) return 1;
     if (!(drift_clip >= 0.0f)) return fail("mala: drift_clip must be >= 0 (got %g)", (double)drift_clip);
     if (chains == 0) return 0;
     const SlotArgs sa = slot_args(nslot, desc, meta, tables, table_floats, prior_kind, prior_a, prior_lognorm);
-    MalaArgs ma;
-    ma.noise = noise;
-    ma.scale = scale;
-    ma.out = out;
     ma.logp = logp;
-    ma.steps = steps;
-    // step g = step_offset + t is kept iff g >= keep_from and (g - keep_from) % keep_every == 0, as row (g - keep_from) / keep_every
-    const int64_t k0 = step_offset - keep_from;
-    const int64_t r = k0 > 0 ? k0 % keep_every : 0;
-    ma.keep_t = k0 <= 0 ? -k0 : (r == 0 ? 0 : keep_every - r);
-    ma.keep_row = k0 <= 0 ? 0 : (k0 + keep_every - 1) / keep_every;
-    if (out == nullptr) ma.keep_t = steps;            // nothing is kept
-    ma.keep_every = keep_every;
-    ma.chains = (int)chains;
-    ma.d = d;
     ma.drift_clip = drift_clip;
     const int G = (int)((chains + MENT_BLOCK - 1) / MENT_BLOCK);
-    if (tl) {
-        MF_ALLOW_DYN_SMEM(mala_ment_steps_kernel<true>, smem);
-        MF_LAUNCH((mala_ment_steps_kernel<true>), G, MENT_BLOCK, smem, stream, x, ma, sa, accepted);
-    } else {
-        MF_ALLOW_DYN_SMEM(mala_ment_steps_kernel<false>, smem);
-        MF_LAUNCH((mala_ment_steps_kernel<false>), G, MENT_BLOCK, smem, stream, x, ma, sa, accepted);
-    }
+    MF_LAUNCH_TAB(tl, mala_ment_steps_kernel<true>, mala_ment_steps_kernel<false>, G, MENT_BLOCK, smem, stream, x, ma, sa,
+                  accepted);
     return check_launch("mf_mala_ment_steps");
 }

@@ -6,7 +6,7 @@
 // the tables, under the rule of ment_slots.h) are staged in LDS once per workgroup.  Per step t (global index
 // g = step_offset + t):
 //   y = fma(scale, noise[t][0..d)[c], x)                     (fp32, one rounding per axis)
-//   p_new = prob(y)                                          (slot_product + prior_factor: the bits mf_ment_prob returns)
+//   p_new = prob(y)                                          (prob_point: the bits mf_ment_prob returns)
 //   u = noise[t][d][c]
 //   accept  iff  p_new > 0 ? u * p < p_new : (p_new == 0 && p == 0)
 // so a chain inside the support never leaves it, a chain outside it (p == 0) random-walks until it finds it, and a NaN p_new
@@ -16,32 +16,12 @@
 // p is recomputed from x at entry: no density buffer crosses the ABI, and p is right when the tables changed between calls.
 // Nothing in a chain depends on another chain or on how the steps are cut into launches (keeping is decided by g alone):
 // outputs are bitwise reproducible and 40 steps in one launch equal 4 launches of 10.  No atomics.
-#include "ment_slots.h"
+#include "ment_chain.h"
 
 namespace mf {
 
-struct McmcArgs {
-    const float* noise;     // [steps][d + 1][chains]
-    const float* scale;     // [d] proposal scale per axis
-    float* out;             // [n_keep][chains][d] or null
-    int64_t steps;
-    int64_t keep_t;         // first step t of this launch that is kept (>= steps: none), formed on the host from step_offset,
-    int64_t keep_row;       // keep_from and keep_every, and the row of `out` it goes to
-    int64_t keep_every;
-    int chains;
-    int d;
-};
-
 template <bool TAB_LDS>
-__device__ __forceinline__ float chain_prob(const float (&xv)[MENT_DMAX], int d, const float* desc, const int* meta,
-                                            const float* tab, const SlotArgs& sa) {
-    float prob = slot_product<TAB_LDS>(xv, d, desc, meta, tab, sa.nslot, 1.0f);
-    if (prob != 0.0f) prob *= prior_factor(xv, d, sa.prior_kind, sa.prior_a, sa.prior_lognorm);
-    return prob;
-}
-
-template <bool TAB_LDS>
-__global__ __launch_bounds__(MENT_BLOCK) void mcmc_ment_steps_kernel(float* __restrict__ x, McmcArgs ma, SlotArgs sa,
+__global__ __launch_bounds__(MENT_BLOCK) void mcmc_ment_steps_kernel(float* __restrict__ x, ChainArgs ma, SlotArgs sa,
                                                                      int* __restrict__ accepted) {
     MF_DYN_SMEM(float, lds);
     float* desc;
@@ -56,32 +36,25 @@ __global__ __launch_bounds__(MENT_BLOCK) void mcmc_ment_steps_kernel(float* __re
         xv[j] = (j < d) ? x[(int64_t)c * d + j] : 0.0f;
         sc[j] = (j < d) ? ma.scale[j] : 0.0f;
     }
-    float p = chain_prob<TAB_LDS>(xv, d, desc, meta, tab, sa);
+    float p = prob_point(xv, d, desc, meta, tab, sa);
     int acc = 0;
     const int64_t row = ma.chains;                     // floats per noise row
     int64_t keep_t = ma.keep_t, keep_row = ma.keep_row;
     for (int64_t t = 0; t < ma.steps; ++t) {
-        const float* nz = ma.noise + t * (d + 1) * row + c;
+        const float* nz = chain_noise(ma, t, c);
         float yv[MENT_DMAX];
 #pragma unroll
         for (int j = 0; j < MENT_DMAX; ++j) {
             yv[j] = (j < d) ? fmaf(sc[j], nz[j * row], xv[j]) : 0.0f;
         }
         const float u = nz[d * row];
-        const float p_new = chain_prob<TAB_LDS>(yv, d, desc, meta, tab, sa);
+        const float p_new = prob_point(yv, d, desc, meta, tab, sa);
         const bool accept = p_new > 0.0f ? (u * p < p_new) : (p_new == 0.0f && p == 0.0f);
 #pragma unroll
         for (int j = 0; j < MENT_DMAX; ++j) xv[j] = accept ? yv[j] : xv[j];
         p = accept ? p_new : p;
         acc += accept ? 1 : 0;
-        if (t == keep_t) {
-            float* o = ma.out + (keep_row * row + c) * d;
-#pragma unroll
-            for (int j = 0; j < MENT_DMAX; ++j)
-                if (j < d) o[j] = xv[j];
-            keep_t += ma.keep_every;
-            ++keep_row;
-        }
+        chain_keep(ma, t, c, xv, keep_t, keep_row);
     }
 #pragma unroll
     for (int j = 0; j < MENT_DMAX; ++j)
@@ -101,34 +74,12 @@ extern "C" int mf_mcmc_ment_steps(float* x, int64_t chains, int d, int nslot, co
     size_t smem;
     bool tl;
     if (slot_geometry(d, nslot, table_floats, prior_kind, &smem, &tl)) return 1;
-    if (chains < 0 || chains > 2147483647LL - MENT_BLOCK) return fail("mcmc: bad chain count %lld", (long long)chains);
-    if (steps < 0 || step_offset < 0 || keep_from < 0) return fail("mcmc: steps, step_offset and keep_from must be >= 0");
-    if (keep_every < 1) return fail("mcmc: keep_every must be >= 1 (got %lld)", (long long)keep_every);
-    const int64_t lim = (int64_t)1 << 40;              // keeps the step arithmetic far from overflow
-    if (steps > lim || step_offset > lim || keep_from > lim || keep_every > lim) return fail("mcmc: step counts beyond 2^40");
+    ChainArgs ma;
+    if (chain_args("mcmc", chains, d, noise, steps, step_offset, scale, keep_from, keep_every, out, &ma)) return 1;
     if (chains == 0) return 0;
     const SlotArgs sa = slot_args(nslot, desc, meta, tables, table_floats, prior_kind, prior_a, prior_lognorm);
-    McmcArgs ma;
-    ma.noise = noise;
-    ma.scale = scale;
-    ma.out = out;
-    ma.steps = steps;
-    // step g = step_offset + t is kept iff g >= keep_from and (g - keep_from) % keep_every == 0, as row (g - keep_from) / keep_every
-    const int64_t k0 = step_offset - keep_from;
-    const int64_t r = k0 > 0 ? k0 % keep_every : 0;
-    ma.keep_t = k0 <= 0 ? -k0 : (r == 0 ? 0 : keep_every - r);
-    ma.keep_row = k0 <= 0 ? 0 : (k0 + keep_every - 1) / keep_every;
-    if (out == nullptr) ma.keep_t = steps;            // nothing is kept
-    ma.keep_every = keep_every;
-    ma.chains = (int)chains;
-    ma.d = d;
     const int G = (int)((chains + MENT_BLOCK - 1) / MENT_BLOCK);
-    if (tl) {
-        MF_ALLOW_DYN_SMEM(mcmc_ment_steps_kernel<true>, smem);
-        MF_LAUNCH((mcmc_ment_steps_kernel<true>), G, MENT_BLOCK, smem, stream, x, ma, sa, accepted);
-    } else {
-        MF_ALLOW_DYN_SMEM(mcmc_ment_steps_kernel<false>, smem);
-        MF_LAUNCH((mcmc_ment_steps_kernel<false>), G, MENT_BLOCK, smem, stream, x, ma, sa, accepted);
-    }
+    MF_LAUNCH_TAB(tl, mcmc_ment_steps_kernel<true>, mcmc_ment_steps_kernel<false>, G, MENT_BLOCK, smem, stream, x, ma, sa,
+                  accepted);
     return check_launch("mf_mcmc_ment_steps");
 }

@@ -19,7 +19,7 @@
 // Determinism: no float atomics anywhere.  Sums (per-block sums of the sampling weights, per-bin integrals) are fp64, each
 // thread's share in a fixed order, then a fixed-shape tree per block, then a fixed-order pass over the blocks: every output
 // is bitwise reproducible from launch to launch.
-#include "ment_slots.h"   // SlotArgs, slot_product, prior_factor, stage_slots, slot_geometry, slot_args (shared with mcmc.hip)
+#include "ment_slots.h"   // SlotArgs, prob_point, stage_slots, slot_geometry, slot_args, MF_LAUNCH_TAB
 
 namespace mf {
 
@@ -54,8 +54,7 @@ __global__ __launch_bounds__(MENT_BLOCK) void ment_prob_points_kernel(const floa
         float xv[MENT_DMAX];
 #pragma unroll
         for (int j = 0; j < MENT_DMAX; ++j) xv[j] = (j < d) ? x[p * d + j] : 0.0f;
-        float prob = slot_product<TAB_LDS>(xv, d, desc, meta, tab, sa.nslot, 1.0f);
-        if (prob != 0.0f) prob *= prior_factor(xv, d, sa.prior_kind, sa.prior_a, sa.prior_lognorm);
+        const float prob = prob_point(xv, d, desc, meta, tab, sa);
         out[p] = multiply ? out[p] * prob : prob;
     }
 }
@@ -98,8 +97,7 @@ __global__ __launch_bounds__(MENT_BLOCK) void ment_prob_grid_kernel(GridArgs g, 
         if (q >= g.ncells) break;
         float xv[MENT_DMAX];
         grid_point(g, (unsigned)q, xv);
-        float prob = slot_product<TAB_LDS>(xv, g.d, desc, meta, tab, sa.nslot, 1.0f);
-        if (prob != 0.0f) prob *= prior_factor(xv, g.d, sa.prior_kind, sa.prior_a, sa.prior_lognorm);
+        const float prob = prob_point(xv, g.d, desc, meta, tab, sa);
         prob_out[q] = prob;
         acc += cell_weight(prob);
     }
@@ -245,9 +243,7 @@ __global__ __launch_bounds__(MENT_BLOCK) void ment_integrate_kernel(IntArgs ia, 
                 if (i < ia.d && j < ia.d) v = fmaf(ia.minv[i * MENT_DMAX + j], uv[j], v);
             xv[i] = v;
         }
-        float prob = slot_product<TAB_LDS>(xv, ia.d, desc, meta, tab, sa.nslot, 1.0f);
-        if (prob != 0.0f) prob *= prior_factor(xv, ia.d, sa.prior_kind, sa.prior_a, sa.prior_lognorm);
-        acc += (double)prob;
+        acc += (double)prob_point(xv, ia.d, desc, meta, tab, sa);
     }
     const double s = block_sum_f64(acc, red);
     if (threadIdx.x == 0) partial[(int64_t)bin * ia.nchunks + blockIdx.x] = s;
@@ -293,13 +289,8 @@ extern "C" int mf_ment_prob(const float* x, int64_t n, int d, int nslot, const f
     if (n == 0) return 0;
     const SlotArgs sa = slot_args(nslot, desc, meta, tables, table_floats, prior_kind, prior_a, prior_lognorm);
     const int G = grid_blocks(n, MENT_BLOCK, NUM_CU * 16);
-    if (tl) {
-        MF_ALLOW_DYN_SMEM(ment_prob_points_kernel<true>, smem);
-        MF_LAUNCH((ment_prob_points_kernel<true>), G, MENT_BLOCK, smem, stream, x, n, d, sa, multiply, out);
-    } else {
-        MF_ALLOW_DYN_SMEM(ment_prob_points_kernel<false>, smem);
-        MF_LAUNCH((ment_prob_points_kernel<false>), G, MENT_BLOCK, smem, stream, x, n, d, sa, multiply, out);
-    }
+    MF_LAUNCH_TAB(tl, ment_prob_points_kernel<true>, ment_prob_points_kernel<false>, G, MENT_BLOCK, smem, stream, x, n, d, sa,
+                  multiply, out);
     return check_launch("mf_ment_prob");
 }
 
@@ -334,13 +325,8 @@ extern "C" int mf_ment_prob_grid(const float* coords, const int64_t* shape, int 
     g.ncells = ncells;
     const SlotArgs sa = slot_args(nslot, desc, meta, tables, table_floats, prior_kind, prior_a, prior_lognorm);
     const int64_t nb = mf_ment_blocks(ncells);
-    if (tl) {
-        MF_ALLOW_DYN_SMEM(ment_prob_grid_kernel<true>, smem);
-        MF_LAUNCH((ment_prob_grid_kernel<true>), dim3((unsigned)nb), MENT_BLOCK, smem, stream, g, sa, prob, block_sums);
-    } else {
-        MF_ALLOW_DYN_SMEM(ment_prob_grid_kernel<false>, smem);
-        MF_LAUNCH((ment_prob_grid_kernel<false>), dim3((unsigned)nb), MENT_BLOCK, smem, stream, g, sa, prob, block_sums);
-    }
+    MF_LAUNCH_TAB(tl, ment_prob_grid_kernel<true>, ment_prob_grid_kernel<false>, dim3((unsigned)nb), MENT_BLOCK, smem, stream, g,
+                  sa, prob, block_sums);
     return check_launch("mf_ment_prob_grid");
 }
 
@@ -425,13 +411,7 @@ extern "C" int mf_ment_integrate(int d, const float* minv, const float* coords, 
         for (int j = 0; j < d; ++j) ia.minv[i * MENT_DMAX + j] = minv[i * d + j];
     const SlotArgs sa = slot_args(nslot, desc, meta, tables, table_floats, prior_kind, prior_a, prior_lognorm);
     const dim3 grid((unsigned)ia.nchunks, (unsigned)nbins);
-    if (tl) {
-        MF_ALLOW_DYN_SMEM(ment_integrate_kernel<true>, smem);
-        MF_LAUNCH((ment_integrate_kernel<true>), grid, MENT_BLOCK, smem, stream, ia, sa, partial);
-    } else {
-        MF_ALLOW_DYN_SMEM(ment_integrate_kernel<false>, smem);
-        MF_LAUNCH((ment_integrate_kernel<false>), grid, MENT_BLOCK, smem, stream, ia, sa, partial);
-    }
+    MF_LAUNCH_TAB(tl, ment_integrate_kernel<true>, ment_integrate_kernel<false>, grid, MENT_BLOCK, smem, stream, ia, sa, partial);
     if (check_launch("mf_ment_integrate")) return 1;
     MF_LAUNCH(ment_integrate_finish_kernel, grid_blocks(nbins, MENT_BLOCK, 1 << 20), MENT_BLOCK, 0, stream,
               (const double*)partial, (int)nbins, ia.nchunks, pred);

@@ -4,9 +4,9 @@
 // fp32's range with a hundred factors long before the log-density stops being meaningful.
 //
 // One lane per point.  x[d <= 8] and the gradient accumulators live in registers; descriptors (and the tables, under the rule
-// of ment_slots.h) are staged in LDS once per workgroup, which then strides over the points.  Per slot, u and the cell (i, w)
-// come from the fmaf chain and grid_pos of slot_product, so the support is bit for bit that of mf_ment_prob, slot order and
-// early exit included: the first zero factor ends the row with -inf, the first NaN factor with NaN.
+// of ment_slots.h) are staged in LDS once per workgroup, which then strides over the points.  Per slot, the factor is
+// slot_value of ment_slots.h, the function mf_ment_prob multiplies, so the support is bit for bit that of mf_ment_prob, slot
+// order and early exit included: the first zero factor ends the row with -inf, the first NaN factor with NaN.
 //
 // Range.  No per-slot log: each factor is split into mantissa and exponent (frexpf: exact), the mantissas are multiplied into a
 // running product in (2^-17, 1] that is renormalised every 16 slots, the exponents are summed in an integer, and one logf per
@@ -35,7 +35,7 @@ __global__ __launch_bounds__(MENT_BLOCK) void ment_logprob_kernel(const float* _
         float xv[MENT_DMAX], g[MENT_DMAX];
 #pragma unroll
         for (int j = 0; j < MENT_DMAX; ++j) xv[j] = (j < d) ? x[p * d + j] : 0.0f;
-        const float lp = logp_point<TAB_LDS, GRAD>(xv, d, desc, meta, tab, sa, inv_a2, g);     // ment_logp_point.h
+        const float lp = logp_point<GRAD>(xv, d, desc, meta, tab, sa, inv_a2, g);     // ment_logp_point.h
         logp[p] = lp;
         if (GRAD) {
 #pragma unroll
@@ -43,13 +43,6 @@ __global__ __launch_bounds__(MENT_BLOCK) void ment_logprob_kernel(const float* _
                 if (j < d) grad[p * d + j] = g[j];
         }
     }
-}
-
-template <bool TAB_LDS, bool GRAD>
-static void launch_logprob(int G, size_t smem, void* stream, const float* x, int64_t n, int d, const SlotArgs& sa, float* logp,
-                           float* grad) {
-    MF_ALLOW_DYN_SMEM((ment_logprob_kernel<TAB_LDS, GRAD>), smem);
-    MF_LAUNCH((ment_logprob_kernel<TAB_LDS, GRAD>), G, MENT_BLOCK, smem, stream, x, n, d, sa, logp, grad);
 }
 
 }  // namespace mf
@@ -68,12 +61,11 @@ extern "C" int mf_ment_logprob(const float* x, int64_t n, int d, int nslot, cons
     int64_t blocks = (n + MENT_BLOCK - 1) / MENT_BLOCK;
     if (blocks > NUM_CU * 16) blocks = NUM_CU * 16;
     const int G = (int)blocks;
-    if (tl) {
-        if (grad) launch_logprob<true, true>(G, smem, stream, x, n, d, sa, logp, grad);
-        else launch_logprob<true, false>(G, smem, stream, x, n, d, sa, logp, grad);
-    } else {
-        if (grad) launch_logprob<false, true>(G, smem, stream, x, n, d, sa, logp, grad);
-        else launch_logprob<false, false>(G, smem, stream, x, n, d, sa, logp, grad);
-    }
+    if (grad)
+        MF_LAUNCH_TAB(tl, (ment_logprob_kernel<true, true>), (ment_logprob_kernel<false, true>), G, MENT_BLOCK, smem, stream, x, n,
+                      d, sa, logp, grad);
+    else
+        MF_LAUNCH_TAB(tl, (ment_logprob_kernel<true, false>), (ment_logprob_kernel<false, false>), G, MENT_BLOCK, smem, stream, x,
+                      n, d, sa, logp, grad);
     return check_launch("mf_ment_logprob");
 }

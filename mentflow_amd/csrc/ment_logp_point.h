@@ -1,51 +1,13 @@
 // Log-density of classical MENT and its gradient at ONE point, shared by the kernels of ment_logp.hip (one lane per point) and
 // mala.hip (one lane per chain, the point is the chain's state or its proposal).  Both call logp_point, so both return the same
-// bits for the same point.  Conventions, range handling and the gradient are described at the top of ment_logp.hip.
+// bits for the same point; the factors come from slot_value of ment_slots.h.  Conventions,
+// range handling and the gradient are described at the top of ment_logp.hip.
 #pragma once
 #include "ment_slots.h"
 
 namespace mf {
 
 constexpr int LOGP_RENORM = 16;        // slots between renormalisations of the running product (a mantissa is >= 1/2)
-
-// h and, when GRAD, its partials along the slot's projected axes, from the arithmetic of slot_product
-template <bool TAB_LDS, bool GRAD>
-__device__ __forceinline__ float slot_value(const float (&xv)[MENT_DMAX], int d, const float* __restrict__ ds,
-                                            const int* __restrict__ ms, const float* __restrict__ tab, float& h0, float& h1) {
-    float u0 = 0.0f;
-#pragma unroll
-    for (int j = 0; j < MENT_DMAX; ++j)
-        if (j < d) u0 = fmaf(xv[j], ds[j], u0);
-    const float* t = tab + ms[3];
-    h0 = 0.0f;
-    h1 = 0.0f;
-    if (ms[0] == 1) {
-        int i;
-        float w;
-        if (u0 != u0) return u0;
-        if (!grid_pos(u0, ds[16], ds[17], ds[18], ms[1], i, w)) return 0.0f;
-        const float a = t[i], b = t[i + 1];
-        if (GRAD) h0 = (b - a) * ds[18];
-        return a * (1.0f - w) + b * w;
-    }
-    float u1 = 0.0f;
-#pragma unroll
-    for (int j = 0; j < MENT_DMAX; ++j)
-        if (j < d) u1 = fmaf(xv[j], ds[8 + j], u1);
-    int i, k;
-    float wx, wy;
-    const int By = ms[2];
-    if (u0 != u0 || u1 != u1) return u0 + u1;
-    if (!grid_pos(u0, ds[16], ds[17], ds[18], ms[1], i, wx) || !grid_pos(u1, ds[19], ds[20], ds[21], By, k, wy)) return 0.0f;
-    const float* r0 = t + i * By + k;
-    const float* r1 = r0 + By;
-    const float v00 = r0[0], v01 = r0[1], v10 = r1[0], v11 = r1[1];
-    if (GRAD) {
-        h0 = ((v10 - v00) * (1.0f - wy) + (v11 - v01) * wy) * ds[18];
-        h1 = ((v01 - v00) * (1.0f - wx) + (v11 - v10) * wx) * ds[21];
-    }
-    return v00 * ((1.0f - wx) * (1.0f - wy)) + v01 * ((1.0f - wx) * wy) + v10 * (wx * (1.0f - wy)) + v11 * (wx * wy);
-}
 
 // 1 / prior_a^2 of a Gaussian prior (0 otherwise): formed once per launch and handed to logp_point
 __device__ __forceinline__ float prior_inv_a2(const SlotArgs& sa) {
@@ -54,7 +16,7 @@ __device__ __forceinline__ float prior_inv_a2(const SlotArgs& sa) {
 
 // logp at xv (xv[d..8) = 0); when GRAD, g[0..d) = d logp / dx, the row of a -inf point 0 and that of a NaN point NaN
 // (g[d..8) carries no meaning).  desc / meta / tab as stage_slots returns them.
-template <bool TAB_LDS, bool GRAD>
+template <bool GRAD>
 __device__ __forceinline__ float logp_point(const float (&xv)[MENT_DMAX], int d, const float* __restrict__ desc,
                                             const int* __restrict__ meta, const float* __restrict__ tab, const SlotArgs& sa,
                                             float inv_a2, float (&g)[MENT_DMAX]) {
@@ -66,7 +28,7 @@ __device__ __forceinline__ float logp_point(const float (&xv)[MENT_DMAX], int d,
     for (int s = 0; s < sa.nslot; ++s) {
         const float* ds = desc + s * MENT_DESC;
         float h0, h1;
-        const float h = clamp_factor(slot_value<TAB_LDS, GRAD>(xv, d, ds, meta + s * MENT_META, tab, h0, h1));
+        const float h = clamp_factor(slot_value<GRAD>(xv, d, ds, meta + s * MENT_META, tab, h0, h1));
         if (h != h) {
             m = h;
             break;

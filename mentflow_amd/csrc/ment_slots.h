@@ -1,6 +1,7 @@
-// Slot machinery of classical MENT shared by the kernels of ment.hip and mcmc.hip: the slot arguments, the product of
-// Lagrange functions at one point, the prior factor, the staging of descriptors (and tables) into LDS and the host-side
-// checks of the slot arguments.  The slot layout and the density are described at the top of ment.hip.
+// Slot machinery of classical MENT shared by every MENT kernel (ment.hip, ment_logp.hip, ment_tabgrad.hip, mcmc.hip, mala.hip):
+// the slot arguments, the evaluation of one slot at one point, the product of Lagrange functions
+// and the density built on it, the prior, the staging of descriptors (and tables) into LDS, the host-side checks of the slot
+// arguments and the dispatch on where the tables live.  The slot layout and the density are described at the top of ment.hip.
 #pragma once
 #include "common.h"
 
@@ -40,10 +41,51 @@ __device__ __forceinline__ bool grid_pos(float u, float c0, float cl, float inv_
     return true;
 }
 
-template <bool TAB_LDS>
+// h of one slot at xv and, when GRAD, its partials along the slot's projected axes.  hipcc contracts a * b + c, and which
+// product of a sum it fuses follows the shape of the code around it: the bits of the partials rest on this function's form.
+template <bool GRAD>
+__device__ __forceinline__ float slot_value(const float (&xv)[MENT_DMAX], int d, const float* __restrict__ ds,
+                                            const int* __restrict__ ms, const float* __restrict__ tab, float& h0, float& h1) {
+    float u0 = 0.0f;
+#pragma unroll
+    for (int j = 0; j < MENT_DMAX; ++j)
+        if (j < d) u0 = fmaf(xv[j], ds[j], u0);
+    const float* t = tab + ms[3];
+    h0 = 0.0f;
+    h1 = 0.0f;
+    if (ms[0] == 1) {
+        int i;
+        float w;
+        if (u0 != u0) return u0;
+        if (!grid_pos(u0, ds[16], ds[17], ds[18], ms[1], i, w)) return 0.0f;
+        const float a = t[i], b = t[i + 1];
+        if (GRAD) h0 = (b - a) * ds[18];
+        return a * (1.0f - w) + b * w;
+    }
+    float u1 = 0.0f;
+#pragma unroll
+    for (int j = 0; j < MENT_DMAX; ++j)
+        if (j < d) u1 = fmaf(xv[j], ds[8 + j], u1);
+    int i, k;
+    float wx, wy;
+    const int By = ms[2];
+    if (u0 != u0 || u1 != u1) return u0 + u1;
+    if (!grid_pos(u0, ds[16], ds[17], ds[18], ms[1], i, wx) || !grid_pos(u1, ds[19], ds[20], ds[21], By, k, wy)) return 0.0f;
+    const float* r0 = t + i * By + k;
+    const float* r1 = r0 + By;
+    const float v00 = r0[0], v01 = r0[1], v10 = r1[0], v11 = r1[1];
+    if (GRAD) {
+        h0 = ((v10 - v00) * (1.0f - wy) + (v11 - v01) * wy) * ds[18];
+        h1 = ((v01 - v00) * (1.0f - wx) + (v11 - v10) * wx) * ds[21];
+    }
+    return v00 * ((1.0f - wx) * (1.0f - wy)) + v01 * ((1.0f - wx) * wy) + v10 * (wx * (1.0f - wy)) + v11 * (wx * wy);
+}
+
+// product of the clamped factors over the slots; a product that has reached 0 skips the remaining slots.  The factor is that of
+// slot_value<false>, written out: through that function the grid kernels measured 0.1-0.3 % slower (profiles/ment_refactor_ab.json)
 __device__ __forceinline__ float slot_product(const float (&xv)[MENT_DMAX], int d, const float* __restrict__ desc,
-                                              const int* __restrict__ meta, const float* __restrict__ tab, int nslot,
-                                              float prob) {
+                                              const int* __restrict__ meta, const float* __restrict__ tab, int nslot) {
+    float prob = 1.0f;
     for (int s = 0; s < nslot; ++s) {
         if (prob == 0.0f) break;
         const float* ds = desc + s * MENT_DESC;
@@ -101,6 +143,14 @@ __device__ __forceinline__ float prior_factor(const float (&xv)[MENT_DMAX], int 
     return 1.0f;
 }
 
+// the density at xv: the bits mf_ment_prob returns (desc / meta / tab as stage_slots returns them)
+__device__ __forceinline__ float prob_point(const float (&xv)[MENT_DMAX], int d, const float* __restrict__ desc,
+                                            const int* __restrict__ meta, const float* __restrict__ tab, const SlotArgs& sa) {
+    float prob = slot_product(xv, d, desc, meta, tab, sa.nslot);
+    if (prob != 0.0f) prob *= prior_factor(xv, d, sa.prior_kind, sa.prior_a, sa.prior_lognorm);
+    return prob;
+}
+
 // Descriptors (+ tables when TAB_LDS) into LDS; returns the table pointer every lane reads.
 template <bool TAB_LDS>
 __device__ __forceinline__ const float* stage_slots(const SlotArgs& sa, float* lds, float*& desc, int*& meta) {
@@ -114,6 +164,18 @@ __device__ __forceinline__ const float* stage_slots(const SlotArgs& sa, float* l
     __syncthreads();
     return TAB_LDS ? tl : sa.tables;
 }
+
+// Launches the tables-in-LDS or the tables-in-global-memory instance of a kernel template, as slot_geometry decided.
+#define MF_LAUNCH_TAB(tab_lds, k_lds, k_global, grid, block, smem, stream, ...)  \
+    do {                                                                          \
+        if (tab_lds) {                                                            \
+            MF_ALLOW_DYN_SMEM(k_lds, smem);                                       \
+            MF_LAUNCH((k_lds), grid, block, smem, stream, __VA_ARGS__);           \
+        } else {                                                                  \
+            MF_ALLOW_DYN_SMEM(k_global, smem);                                    \
+            MF_LAUNCH((k_global), grid, block, smem, stream, __VA_ARGS__);        \
+        }                                                                         \
+    } while (0)
 
 // checks the slot arguments; *lds_bytes = dynamic LDS of the launch, *tab_lds = whether the tables go there
 static int slot_geometry(int d, int nslot, int64_t table_floats, int prior_kind, size_t* lds_bytes, bool* tab_lds) {

@@ -7,8 +7,8 @@
 // both in [0, 1], summing to 1 (four such terms for a 2-D slot).  So
 //     grad_log[e] = sum_n weight[n] rho_e(n),      grad_tab[e] = grad_log[e] / tables[e].
 //
-// One lane per point, striding as ment_logprob_kernel does.  Projections and cells come from the fmaf chain of slot_value and
-// from grid_pos (ment_logp_point.h, ment_slots.h): the cell is bit for bit the one the forward used.  A row takes part iff its
+// One lane per point, striding as ment_logprob_kernel does.  Projections and cells come from the fmaf chain and the grid_pos
+// calls of slot_value (ment_slots.h), restated here because the kernel needs the cell itself: the cell is that of the forward.  A row takes part iff its
 // logp (as the forward returned it) is finite and its weight is not zero, so every slot of a live row has a positive factor.
 //
 // Accumulation is FIXED POINT (kde.hip's scheme, signed): with P = 2^ceil(log2 wmax) >= max |weight| and
@@ -24,7 +24,7 @@
 //   global  descriptors in LDS, tables read from global memory, 64-bit integer global atomics straight into `acc`.
 #include <float.h>
 
-#include "ment_logp_point.h"
+#include "ment_slots.h"
 
 namespace mf {
 
