@@ -366,6 +366,35 @@ int mf_mala_ment_steps(float* x, int64_t chains, int d, int nslot, const float* 
                        int64_t keep_every, float* out, int32_t* accepted, float* logp, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Annealed importance sampling on the density of classical MENT (no counterpart in the reference): log-weights whose mean
+ * estimates the normaliser of the density.  A purely additive entry point: MF_ABI_VERSION stays 5.  Slot arguments (nslot ..
+ * prior_lognorm) exactly as mf_ment_prob takes them; x, scale, drift_clip, accepted and logp exactly as mf_mala_ment_steps.
+ *
+ * mf_ais_ment_steps: `chains` independent chains, one GPU lane each, walk the temperatures k = temp_offset + 1 .. temp_offset +
+ *                    ntemps of the ladder betas[nbetas] (device, non-decreasing in [0, 1]; temp_offset + ntemps < nbetas) from
+ *                    x[chains, d] (in / out).  lp = logp(x) and g its gradient as mf_ment_logprob returns them (the same
+ *                    device function: the same bits).  The base q0 = N(base_mean, diag base_scale^2) (HOST arrays [d],
+ *                    base_scale > 0) has lq(x) = c0 - 0.5 sum t_j^2, t_j = (x_j - m_j) * (1 / b_j), c0 = -sum log b_j -
+ *                    (d / 2) log 2 pi formed in fp64, and gradient gq_j = -(t_j * (1 / b_j)).  The tempered density is
+ *                    l_b = b > 0 ? lq + b * (lp - lq) : lq with gradient gb = gq + b * (g - gq) (b == 0: gq; 0 where
+ *                    l_b == -inf), all in fp32, one rounding per operation.  Per temperature k:
+ *                      logw[c] += betas[k] == betas[k-1] ? 0 : (lp > -inf ? (betas[k] - betas[k-1]) * (lp - lq) : -inf)
+ *                    (fp32 increment, fp64 sum: logw double[chains], in / out, may reach -inf, never NaN), then
+ *                    steps_per_temp >= 0 transitions of mf_mala_ment_steps with l -> l_b and g -> gb at b = betas[k]: same
+ *                    proposal, truncated drift, acceptance rule and NaN conventions.  noise[ntemps * steps_per_temp][d + 1]
+ *                    [chains] holds this call's transitions in order.  out (may be NULL) [total transitions][chains][d]
+ *                    receives the state after every transition, at row temp_offset * steps_per_temp + its index in this
+ *                    call.  logp (may be NULL) [chains] receives logp of the final states.  lp, g and lq are recomputed at
+ *                    entry: nothing but x and logw crosses a call, and a ladder cut into several calls (temp_offset advanced)
+ *                    gives the bits of one call.  No atomics; chains do not interact; outputs are bitwise reproducible.
+ *                    chains == 0 and ntemps == 0 do nothing.  ntemps, temp_offset, steps_per_temp <= 2^20.                 */
+int mf_ais_ment_steps(float* x, int64_t chains, int d, int nslot, const float* desc, const int32_t* meta, const float* tables,
+                      int64_t table_floats, int prior_kind, float prior_a, float prior_lognorm, const float* noise,
+                      const float* betas, int64_t nbetas, int64_t ntemps, int64_t temp_offset, int64_t steps_per_temp,
+                      const float* scale, float drift_clip, const float* base_mean, const float* base_scale, double* logw,
+                      float* out, int32_t* accepted, float* logp, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Differentiable log-density of classical MENT (no counterpart in the reference, whose interpolators are scipy on the host).
  * A purely additive entry point: MF_ABI_VERSION stays 5.  Slot arguments (nslot .. prior_lognorm) and limits exactly as
  * mf_ment_prob takes them; n = 0 and nslot = 0 are valid.

@@ -216,6 +216,7 @@ class MENT:
         self.n_samples = int(n_samples)
         self.interpolation = interpolation
         self.lagrange_functions = self.initialize_lagrange_functions()
+        self.log_z: Optional[torch.Tensor] = None            # log of the normaliser, once log_normalization has estimated it
 
     def send(self, x):
         return x.type(torch.float32).to(self.device)
@@ -362,7 +363,7 @@ class MENT:
     def log_prob(self, x: torch.Tensor, pad: float = 1.00e-12) -> torch.Tensor:
         return torch.log(self.prob(x) + pad)
 
-    def log_density(self, x: torch.Tensor, pad: float = 0.0) -> torch.Tensor:
+    def log_density(self, x: torch.Tensor, pad: float = 0.0, normalized: bool = False) -> torch.Tensor:
         """log of the (unnormalised) density of ``prob``, differentiable in x and in the Lagrange tables
         (``lagrange_functions[i][j].values``): the sum over all slots of log clamp(h, 0, 1e10) plus ``prior.log_prob(x)``, from
         ops.MentLogProbFn per pre-transform chain (autograd runs through the chain's pre-transforms) and, for the slots outside
@@ -379,7 +380,12 @@ class MENT:
         under ``gauss_seidel_update``), a factor on the upper clamp is a constant, and rows outside the support pass nothing.
         That makes the MENT dual log Z(exp lambda) - sum g_hat Delta lambda an ordinary autograd objective in lambda = log
         values (examples/fit_ment_dual.py).  ``pad > 0`` returns logaddexp(log_density, log pad), which is log(prob + pad)
-        wherever that is representable.  No host synchronisation: the call, and its backward, can be captured in a graph."""
+        wherever that is representable.  ``normalized=True`` subtracts the ``log_z`` that ``log_normalization`` stored (a
+        ``RuntimeError`` if it has not run): the log of a density that integrates to 1, up to the error of that estimate, which
+        does not follow later changes of the tables.  No host synchronisation: the call, and its backward, can be captured in a
+        graph."""
+        if normalized and getattr(self, "log_z", None) is None:
+            raise RuntimeError("MENT.log_density(normalized=True): no log Z has been estimated yet; call log_normalization() first")
         chains, torch_slots = self._get_plan()
         x = x.to(torch.float32)
         prior = _prior_args(self.prior)
@@ -412,7 +418,47 @@ class MENT:
         total = torch.where(torch.isneginf(total), torch.full_like(total, float("-inf")), total)
         if pad > 0.0:
             total = torch.logaddexp(total, torch.full_like(total, math.log(pad)))
+        if normalized:
+            total = total - self.log_z.to(total.device)
         return total
+
+    def log_normalization(self, sampler: Optional[Callable] = None, **kws) -> dict:
+        """Estimate the normaliser Z = integral of exp(log_density) by annealed importance sampling and return, as 0-dim fp64
+        tensors on the device (no host synchronisation), with w_i = exp(logw_i) the weights of the C chains, w_bar their mean and
+        wt_i = w_i / sum w:
+
+          log_z        logsumexp(logw) - log C, the log of the unbiased estimate w_bar of Z;
+          ess          (sum w)^2 / sum w^2, the effective number of chains (C for equal weights);
+          log_z_se     sqrt(sum (w_i / w_bar - 1)^2) / C, the standard error of log_z by the delta method;
+          entropy      log_z - sum wt_i log_density(x_i), the entropy -integral (p / Z) log (p / Z) of the normalised density from
+                       the weighted final states (rows of weight 0 contribute 0);
+          accept_rate  the share of accepted Langevin transitions.
+
+        ``sampler`` is a :class:`mentflow_amd.sample.AnnealedImportanceSampler` (default: one built from ``**kws``, e.g.
+        ``chains``, ``n_temps``, ``steps_per_temp``, ``step``, ``base_scale``, ``seed``).  ``log_z`` is stored as ``self.log_z``
+        for ``log_density(normalized=True)``.  Only a MENT whose slots all run through the kernels on plain LinearTransforms
+        is supported: one with slots behind a pre-transform chain, or evaluated in torch, raises ``NotImplementedError``."""
+        from .sample import AnnealedImportanceSampler
+        if not self.fully_fused():
+            raise NotImplementedError("MENT.log_normalization: this MENT has slots behind a pre-transform chain or evaluated in "
+                                      "torch; only the single kernel chain of plain LinearTransforms is supported")
+        if sampler is None:
+            sampler = AnnealedImportanceSampler(self.ndim, device=self._device(), **kws)
+        elif kws:
+            raise TypeError("MENT.log_normalization: pass either a sampler or the arguments to build one, not both")
+        res = sampler.run(self)
+        logw, lp = res["logw"], res["logp"].double()
+        chains = logw.numel()
+        lse = torch.logsumexp(logw, 0)
+        wt = torch.exp(logw - lse)                            # normalised weights: they sum to 1
+        log_z = lse - math.log(chains)
+        ess = 1.0 / (wt * wt).sum()
+        log_z_se = torch.sqrt(((chains * wt - 1.0) ** 2).sum()) / chains
+        entropy = log_z - torch.where(wt > 0, wt * lp, torch.zeros_like(wt)).sum()
+        total = max(1, sampler.n_temps * sampler.steps_per_temp) * chains
+        self.log_z = log_z
+        return dict(log_z=log_z, ess=ess, log_z_se=log_z_se, entropy=entropy,
+                    accept_rate=res["accepted"].sum().double() / float(total))
 
     def table_responsibilities(self, x: torch.Tensor, weights: Optional[torch.Tensor] = None) -> List[List[torch.Tensor]]:
         """sum_n w_n rho(x_n) per slot, in the shape of each table: rho is the share of the slot's interpolant that a node of

@@ -702,6 +702,46 @@ def mala_ment_steps(x: torch.Tensor, desc: torch.Tensor, meta: torch.Tensor, tab
          keep_every, ptr(out), ptr(accepted), ptr(logp), stream_ptr(x))
 
 
+def ais_ment_steps(x: torch.Tensor, desc: torch.Tensor, meta: torch.Tensor, tables: torch.Tensor, prior, noise: torch.Tensor,
+                   betas: torch.Tensor, steps_per_temp: int, scale: torch.Tensor, base_mean, base_scale, logw: torch.Tensor,
+                   accepted: torch.Tensor, drift_clip: float = 1.0, temp_offset: int = 0, ntemps: Optional[int] = None,
+                   out: Optional[torch.Tensor] = None, logp: Optional[torch.Tensor] = None) -> None:
+    """Walk the annealed-importance-sampling chains x[chains, d] IN PLACE through `ntemps` temperatures of the ladder
+    betas[K + 1] (float32 on the device, non-decreasing in [0, 1]) from index temp_offset on (default: to the end of the
+    ladder), from the Gaussian base N(base_mean, diag base_scale^2) (host sequences of d floats) towards the MENT density of
+    the slots (mf_ais_ment_steps, include/mentflow_hip.h).  Per temperature logw[chains] (float64, in / out) takes its
+    increment and the chains take steps_per_temp >= 0 Langevin transitions on the tempered density, with scale, drift_clip,
+    accepted and logp as mala_ment_steps takes them.  noise[ntemps * steps_per_temp, d + 1, chains]; out (or None)
+    [>= (temp_offset + ntemps) * steps_per_temp, chains, d] receives the state after every transition at its global row."""
+    name = "ais_ment_steps"
+    steps_per_temp, temp_offset = int(steps_per_temp), int(temp_offset)
+    if betas.dim() != 1 or betas.dtype != _F32 or betas.numel() < 1:
+        raise RuntimeError(f"{name}: betas must be float32[K + 1] (got {betas.dtype}{tuple(betas.shape)})")
+    ntemps = betas.numel() - 1 - temp_offset if ntemps is None else int(ntemps)
+    if steps_per_temp < 0 or temp_offset < 0 or ntemps < 0 or temp_offset + ntemps + 1 > betas.numel():
+        raise RuntimeError(f"{name}: steps_per_temp >= 0 and 0 <= temp_offset <= temp_offset + ntemps <= {betas.numel() - 1} "
+                           f"expected (got {steps_per_temp}, {temp_offset}, {ntemps})")
+    if noise.dim() == 3 and noise.shape[0] != ntemps * steps_per_temp:
+        raise RuntimeError(f"{name}: noise[{ntemps * steps_per_temp}, d + 1, chains] expected (got {tuple(noise.shape)})")
+    chains, d = _check_chain_steps(name, x, desc, meta, tables, noise, scale, accepted, temp_offset * steps_per_temp, 0, 1, out,
+                                   extra=(logp, logw, betas))[:2]
+    drift_clip = float(drift_clip)
+    if not drift_clip >= 0.0:
+        raise RuntimeError(f"{name}: drift_clip >= 0 expected (got {drift_clip})")
+    if logp is not None and (logp.dtype != _F32 or tuple(logp.shape) != (chains,)):
+        raise RuntimeError(f"{name}: logp must be float32[{chains}] (got {logp.dtype}{tuple(logp.shape)})")
+    if logw is None or logw.dtype != torch.float64 or tuple(logw.shape) != (chains,):
+        raise RuntimeError(f"{name}: logw must be float64[{chains}]")
+    mean, base = [float(v) for v in base_mean], [float(v) for v in base_scale]
+    if len(mean) != d or len(base) != d or not all(0.0 < b < math.inf for b in base) or any(m != m for m in mean):
+        raise RuntimeError(f"{name}: base_mean[{d}] and base_scale[{d}] > 0 expected (got {mean}, {base})")
+    mh, bh = (C.c_float * d)(*mean), (C.c_float * d)(*base)
+    call("mf_ais_ment_steps", ptr(x), chains, d, desc.shape[0], ptr(desc), ptr(meta), ptr(tables), tables.numel(),
+         int(prior[0]), float(prior[1]), float(prior[2]), ptr(noise), ptr(betas), betas.numel(), ntemps, temp_offset,
+         steps_per_temp, ptr(scale), drift_clip, C.cast(mh, C.c_void_p), C.cast(bh, C.c_void_p), ptr(logw), ptr(out),
+         ptr(accepted), ptr(logp), stream_ptr(x))
+
+
 def ment_logprob(x: torch.Tensor, desc: torch.Tensor, meta: torch.Tensor, tables: torch.Tensor, prior=(0, 0.0, 0.0),
                  want_grad: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """(logp[n], grad[n, d] or None) of mf_ment_logprob (include/mentflow_hip.h): the sum over slots of log clamp(h, 0, 1e10)

@@ -17,6 +17,9 @@ Metropolis-Hastings chains instead: it needs point evaluations of the density on
 Same call contract as ``GridSampler``; kernel in mentflow_amd/csrc/mcmc.hip.  ``LangevinSampler`` (no counterpart either) pushes
 those proposals along the gradient of the log-density and tests acceptance on logarithms (Metropolis-adjusted Langevin; kernel in
 mentflow_amd/csrc/mala.hip).  Both derive from ``_ChainSampler``, which holds everything but the transition.
+``AnnealedImportanceSampler`` (no counterpart either) walks such Langevin chains along a temperature ladder from a normalised
+Gaussian to the MENT density and carries an importance weight per chain: the weights estimate the normaliser of the density
+(``MENT.log_normalization``), and the weighted final states, resampled, are draws from it (kernel in mentflow_amd/csrc/ais.hip).
 """
 from __future__ import annotations
 
@@ -389,3 +392,138 @@ class LangevinSampler(_ChainSampler):
             if out is not None and k >= 0 and k % keep_every == 0:
                 out[k // keep_every] = x
         self.state = x.contiguous()
+
+
+_AIS_NOISE_BYTES = 64 << 20         # noise of one launch of the ladder (the cut does not change a bit of the result)
+
+
+class AnnealedImportanceSampler:
+    """Annealed importance sampling (Neal 2001) on the density of a fully fused :class:`mentflow_amd.ment.MENT`: `chains`
+    independent chains start from exact draws of a normalised Gaussian base q0 = N(base_mean, diag base_scale^2) and walk the
+    ladder ``betas`` (0 = the base, 1 = the MENT density p) through the tempered densities q0^(1 - beta) p^beta.  At every
+    temperature a chain's log-weight takes (beta_k - beta_{k-1}) (log p - log q0) at its state, then the chain takes
+    ``steps_per_temp`` Langevin transitions (those of ``LangevinSampler``: same proposal, truncated drift and acceptance rule)
+    on the tempered density.  The mean of the weights is an unbiased estimate of Z = integral of p, whatever the ladder and
+    however short the moves; ``MENT.log_normalization`` turns them into log Z, an effective sample size and the entropy.
+
+    Kernel in mentflow_amd/csrc/ais.hip (state, log-density, gradient and log-weight in registers; one launch per block of
+    temperatures whose noise fits _AIS_NOISE_BYTES).  There is no generic path: only the single kernel chain of a MENT whose
+    slots all run through the kernels is taken, anything else raises ``NotImplementedError``.
+
+    ``base_scale=None`` takes the scale of a Gaussian prior, or 1.0 per axis under the box prior; chains that start outside
+    the support get weight 0.  ``betas=None`` is ``linspace(0, 1, n_temps + 1)``; a ladder of one's own must start at 0, end
+    at 1 and not decrease.  ``seed`` fixes the noise (a generator of its own per run), else the device's default generator
+    is used.  ``sampler(prob_func, size)`` runs the ladder and returns ``size`` points resampled from the weighted final
+    states by systematic resampling with one uniform, so the class serves as ``MENT(sampler=...)``."""
+
+    def __init__(self, ndim: int, chains: int = 4096, n_temps: int = 64, steps_per_temp: int = 2,
+                 step: Union[float, Sequence[float]] = 0.25, drift_clip: float = 1.0, base_mean=None, base_scale=None,
+                 betas=None, seed: Optional[int] = None, device: torch.device = None) -> None:
+        name = type(self).__name__
+        self.ndim, self.chains, self.steps_per_temp = int(ndim), int(chains), int(steps_per_temp)
+        if not 1 <= self.ndim <= 8:
+            raise ValueError(f"{name}: 1 <= ndim <= 8 expected (got {ndim})")
+        if self.chains < 1 or self.steps_per_temp < 0:
+            raise ValueError(f"{name}: chains >= 1 and steps_per_temp >= 0 expected")
+        self.step = [float(step)] * self.ndim if isinstance(step, (int, float)) else [float(v) for v in step]
+        if len(self.step) != self.ndim or not all(v > 0 for v in self.step):
+            raise ValueError(f"{name}: step must be a positive float or {self.ndim} positive per-axis scales (got {step})")
+        self.drift_clip = float(drift_clip)
+        if not self.drift_clip >= 0.0:
+            raise ValueError(f"{name}: drift_clip >= 0 expected (got {drift_clip})")
+        if betas is None:
+            if int(n_temps) < 1:
+                raise ValueError(f"{name}: n_temps >= 1 expected (got {n_temps})")
+            betas = torch.linspace(0.0, 1.0, int(n_temps) + 1)
+        betas = torch.as_tensor(betas, dtype=torch.float32).detach().cpu().reshape(-1)
+        if betas.numel() < 2 or float(betas[0]) != 0.0 or float(betas[-1]) != 1.0 or not bool((betas[1:] >= betas[:-1]).all()):
+            raise ValueError(f"{name}: betas must start at 0, end at 1 and not decrease")
+        self.betas = betas
+        self.n_temps = betas.numel() - 1
+        self.base_mean = self._per_axis(base_mean, 0.0, "base_mean")
+        self.base_scale = None if base_scale is None else self._per_axis(base_scale, 1.0, "base_scale")
+        if self.base_scale is not None and not all(0.0 < b < math.inf for b in self.base_scale):
+            raise ValueError(f"{name}: base_scale > 0 expected on every axis (got {self.base_scale})")
+        self.seed = None if seed is None else int(seed)
+        self.device = device
+        self.acceptance: Optional[torch.Tensor] = None
+        self.last: Optional[dict] = None                 # what the latest run returned
+        self._gen: Optional[torch.Generator] = None      # the latest run's generator: __call__ draws its one uniform from it
+
+    def _per_axis(self, value, default: float, what: str) -> List[float]:
+        if value is None:
+            return [default] * self.ndim
+        if isinstance(value, (int, float)):
+            return [float(value)] * self.ndim
+        out = [float(v) for v in value]
+        if len(out) != self.ndim:
+            raise ValueError(f"{type(self).__name__}: {what} must be a float or {self.ndim} per-axis values (got {len(out)})")
+        return out
+
+    def to(self, device):
+        self.device = device
+        return self
+
+    def run(self, ment) -> dict:
+        """Walk the whole ladder on `ment` and return ``x`` [chains, ndim] (the final states), ``logw`` [chains] float64 (the
+        log-weights), ``logp`` [chains] (``ment.log_density`` of the final states, as the kernel carries it) and ``accepted``
+        [chains] int32, all on the device.  No host synchronisation."""
+        from .ment import MENT
+        from .prior import Gaussian
+        name = type(self).__name__
+        if not isinstance(ment, MENT):
+            raise TypeError(f"{name}.run takes a MENT (got {type(ment).__name__})")
+        if ment.ndim != self.ndim:
+            raise ValueError(f"{name}(ndim={self.ndim}) called with a MENT of ndim={ment.ndim}")
+        args = ment.fused_args()
+        if args is None:
+            raise NotImplementedError(f"{name}: this MENT has slots behind a pre-transform chain or evaluated in torch; only a "
+                                      "MENT whose slots all run through the kernels on plain LinearTransforms is supported")
+        device = torch.device(self.device) if self.device is not None else ment._device()
+        base = self.base_scale
+        if base is None:
+            base = [float(ment.prior.scale)] * self.ndim if isinstance(ment.prior, Gaussian) else [1.0] * self.ndim
+        gen = None
+        if self.seed is not None:
+            gen = torch.Generator(device=device)
+            gen.manual_seed(self.seed)
+        d, chains, spt = self.ndim, self.chains, self.steps_per_temp
+        mean_t = torch.tensor(self.base_mean, dtype=torch.float32, device=device)
+        base_t = torch.tensor(base, dtype=torch.float32, device=device)
+        x = (mean_t + base_t * torch.randn(chains, d, device=device, generator=gen)).contiguous()
+        _lib.ptr(x)                                            # the usual refusal of tensors the library does not compute on
+        betas = self.betas.to(device)
+        scale = torch.tensor(self.step, dtype=torch.float32, device=device)
+        logw = torch.zeros(chains, dtype=torch.float64, device=device)
+        logp = torch.empty(chains, dtype=torch.float32, device=device)
+        accepted = torch.zeros(chains, dtype=torch.int32, device=device)
+        per = max(1, _AIS_NOISE_BYTES // (4 * (d + 1) * chains * max(1, spt)))
+        for k0 in range(0, self.n_temps, per):
+            k1 = min(self.n_temps, k0 + per)
+            nz = torch.empty((k1 - k0) * spt, d + 1, chains, device=device)
+            for k in range(k1 - k0):                           # drawn per temperature: the stream does not depend on the cut
+                nz[k * spt:(k + 1) * spt, :d].normal_(generator=gen)
+                nz[k * spt:(k + 1) * spt, d].uniform_(generator=gen)
+            ops.ais_ment_steps(x, args[0], args[1], args[2], args[3], nz, betas, spt, scale, self.base_mean, base, logw,
+                               accepted, drift_clip=self.drift_clip, temp_offset=k0, ntemps=k1 - k0, logp=logp)
+        self.acceptance = accepted.sum().to(torch.float32) / float(max(1, self.n_temps * spt) * chains)
+        self.last = dict(x=x, logw=logw, logp=logp, accepted=accepted)
+        self._gen = gen
+        return self.last
+
+    def __call__(self, prob_func: Callable, size: int) -> torch.Tensor:
+        from .ment import MENT
+        owner = getattr(prob_func, "__self__", None)
+        if not isinstance(owner, MENT) or getattr(prob_func, "__func__", None) is not MENT.prob:
+            raise NotImplementedError(f"{type(self).__name__} takes the bound MENT.prob of a MENT (got "
+                                      f"{getattr(prob_func, '__qualname__', prob_func)}): there is no generic path")
+        res = self.run(owner)
+        x, logw = res["x"], res["logw"]
+        size = int(size)
+        # systematic resampling: the points (u + i) / size, one uniform u, through the cumulative normalised weights
+        w = torch.exp(logw - logw.max())
+        cdf = torch.cumsum(w, 0)
+        u = torch.rand(1, dtype=torch.float64, device=x.device, generator=self._gen)
+        pos = (u + torch.arange(size, dtype=torch.float64, device=x.device)) * (cdf[-1] / size)
+        idx = torch.searchsorted(cdf, pos, right=True).clamp_(max=self.chains - 1)
+        return x[idx]
