@@ -594,7 +594,10 @@ def ment_block_sums(prob: torch.Tensor) -> torch.Tensor:
 def ment_sample(prob: torch.Tensor, shape, block_sums: torch.Tensor, edges: List[torch.Tensor], size: int, noise: bool,
                 rnd: Optional[torch.Tensor] = None) -> torch.Tensor:
     """x[size, len(shape)]: cells drawn with probability (prob + 1e-15) / sum, points uniform in the cell (+ the
-    0.5 U(-delta, delta) noise per axis).  rnd: [size, 1 + 2 d] uniforms (default torch.rand on the device)."""
+    0.5 U(-delta, delta) noise per axis).  rnd: [size, 1 + 2 d] uniforms (default torch.rand on the device): column 0
+    picks the cell by inverse CDF, columns 1..d place the point, columns d+1..2d are the noise.  A cell with prob = 0
+    keeps the weight 1e-15, so rnd[:, 0] = 0 draws cell 0 whatever prob[0] is.  Column 0 is one fp32 number: a draw
+    resolves the CDF to 2^-24 of its total, and at most 2^24 distinct cells can be reached."""
     prob = _f32c(prob.reshape(-1))
     d = len(shape)
     if rnd is None:
