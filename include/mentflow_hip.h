@@ -395,6 +395,31 @@ int mf_ais_ment_steps(float* x, int64_t chains, int d, int nslot, const float* d
                       float* out, int32_t* accepted, float* logp, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * The resampling stage of a sequential Monte Carlo sampler on the density of classical MENT (no counterpart in the reference):
+ * between two calls of mf_ais_ment_steps, which moves the chains and carries their log-weights.  A purely additive entry
+ * point: MF_ABI_VERSION stays 5.
+ *
+ * mf_smc_resample: systematic resampling of the `chains` weighted states x[chains, d] (1 <= d <= 8), split into `groups`
+ *                  islands of S = chains / groups consecutive chains (chains % groups == 0); every island is independent of
+ *                  every other.  Per island g, with m = max logw over it and w_i = exp(logw_i - m) in fp64 (a logw that is
+ *                  NaN or infinite counts as weight 0): S1 = sum w, S2 = sum w^2, ess = S1^2 / S2 (0 if S1 == 0), log mean
+ *                  weight = m + log(S1 / S) (-inf if S1 == 0); stats double[groups][4] receives log mean weight, ess,
+ *                  resampled (0 or 1) and m.  The island resamples iff S1 > 0 and ess < (double)ess_threshold * S (never
+ *                  with a NaN threshold).  If not: its rows of x_out are copies of x, its ancestors are the identity and
+ *                  its logw is untouched, bit for bit.  If so: with the inclusive prefix sums P_i of w (scratch double[chains]),
+ *                  c = S1 / S and u[g] (device, double; clamped into [0, 1 - 2^-53], NaN -> 0), the parent of row j = 0 ..
+ *                  S - 1 is the first i with fma(-j, c, P_i) > u[g] c, that is P_i > (u[g] + j) c, searchsorted from the
+ *                  right, without the rounding of u + j (equal weights give the identity for every u); where rounding
+ *                  leaves none it is the first i with P_i == S1, the last state whose weight moved the prefix.  A state of
+ *                  weight 0 is never a parent; parents do not decrease within an island.  x_out[j] = x[parent] bitwise,
+ *                  ancestors int32[chains] holds the global index of each row's parent, and every logw of the island
+ *                  becomes its log mean weight, so logsumexp(logw) - log S is kept.  Every sum is taken in a fixed order
+ *                  (thread segments, then the segment totals in order); no atomics; outputs are bitwise reproducible and
+ *                  island g's depend on nothing but its own rows and u[g].  x_out must not be x.  chains == 0 does nothing. */
+int mf_smc_resample(const float* x, float* x_out, int64_t chains, int d, int64_t groups, double* logw, const double* u,
+                    float ess_threshold, int32_t* ancestors, double* stats, double* scratch, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Differentiable log-density of classical MENT (no counterpart in the reference, whose interpolators are scipy on the host).
  * A purely additive entry point: MF_ABI_VERSION stays 5.  Slot arguments (nslot .. prior_lognorm) and limits exactly as
  * mf_ment_prob takes them; n = 0 and nslot = 0 are valid.

@@ -97,6 +97,7 @@ PROTOTYPES = {
                                   _i64, _i64, _ptr, _ptr, _ptr, _ptr]),
     "mf_ais_ment_steps": (_i32, [_ptr, _i64, _i32, _i32, _ptr, _ptr, _ptr, _i64, _i32, _f32, _f32, _ptr, _ptr, _i64, _i64, _i64,
                                  _i64, _ptr, _f32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "mf_smc_resample": (_i32, [_ptr, _ptr, _i64, _i32, _i64, _ptr, _ptr, _f32, _ptr, _ptr, _ptr, _ptr]),
     "mf_ment_logprob": (_i32, [_ptr, _i64, _i32, _i32, _ptr, _ptr, _ptr, _i64, _i32, _f32, _f32, _ptr, _ptr, _ptr]),
     "mf_ment_logprob_tables_bwd": (_i32, [_ptr, _i64, _i32, _i32, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr,
                                           _ptr]),

@@ -436,7 +436,11 @@ class MENT:
 
         ``sampler`` is a :class:`mentflow_amd.sample.AnnealedImportanceSampler` (default: one built from ``**kws``, e.g.
         ``chains``, ``n_temps``, ``steps_per_temp``, ``step``, ``base_scale``, ``seed``).  ``log_z`` is stored as ``self.log_z``
-        for ``log_density(normalized=True)``.  Only a MENT whose slots all run through the kernels on plain LinearTransforms
+        for ``log_density(normalized=True)``.  A :class:`mentflow_amd.sample.SequentialMonteCarloSampler` is passed as
+        ``sampler``; its result carries ``log_z_groups``, the estimates of its G independent islands, and then ``log_z`` is
+        logsumexp(log_z_groups) - log G and ``log_z_se`` is std(exp(log_z_groups - log_z), unbiased) / sqrt(G) (NaN for G = 1):
+        the spread of independent estimates, valid however often the chains were resampled, which the delta method over chains
+        is not.  ``ess`` and ``entropy`` come from the final weights as before.  Only a MENT whose slots all run through the kernels on plain LinearTransforms
         is supported: one with slots behind a pre-transform chain, or evaluated in torch, raises ``NotImplementedError``."""
         from .sample import AnnealedImportanceSampler
         if not self.fully_fused():
@@ -454,6 +458,11 @@ class MENT:
         log_z = lse - math.log(chains)
         ess = 1.0 / (wt * wt).sum()
         log_z_se = torch.sqrt(((chains * wt - 1.0) ** 2).sum()) / chains
+        if "log_z_groups" in res:                             # independent islands: their mean, and its error from their spread
+            lzg = res["log_z_groups"]
+            groups = lzg.numel()
+            log_z = torch.logsumexp(lzg, 0) - math.log(groups)
+            log_z_se = torch.exp(lzg - log_z).std(unbiased=True) / math.sqrt(groups) if groups > 1 else log_z * float("nan")
         entropy = log_z - torch.where(wt > 0, wt * lp, torch.zeros_like(wt)).sum()
         total = max(1, sampler.n_temps * sampler.steps_per_temp) * chains
         self.log_z = log_z

@@ -745,6 +745,39 @@ def ais_ment_steps(x: torch.Tensor, desc: torch.Tensor, meta: torch.Tensor, tabl
          ptr(accepted), ptr(logp), stream_ptr(x))
 
 
+def smc_resample(x: torch.Tensor, logw: torch.Tensor, u: torch.Tensor, groups: int,
+                 ess_threshold: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(x_out[chains, d], ancestors int32[chains], stats float64[groups, 4]) of mf_smc_resample (include/mentflow_hip.h):
+    systematic resampling of the weighted states x[chains, d] in `groups` islands of chains / groups consecutive chains, each
+    from its own uniform u[groups] (float64 on the device) and only where its effective sample size is below ess_threshold
+    times its size.  logw[chains] (float64) is updated IN PLACE: the log-weights of an island that resampled all become its
+    log mean weight, those of the others keep their bits.  stats[g] = (log mean weight, ess, resampled 0 / 1, max logw).  No
+    host synchronisation: every decision is taken on the device."""
+    name = "smc_resample"
+    if x.dim() != 2 or not 1 <= x.shape[1] <= 8:
+        raise RuntimeError(f"{name}: x[chains, d <= 8] expected (got {tuple(x.shape)})")
+    chains, d = x.shape
+    groups = int(groups)
+    if x.dtype != _F32:
+        raise RuntimeError(f"{name}: x must be float32 (got {x.dtype})")
+    if groups < 1 or chains % groups != 0:
+        raise RuntimeError(f"{name}: groups >= 1 that divides the {chains} chains expected (got {groups})")
+    if logw is None or logw.dtype != torch.float64 or tuple(logw.shape) != (chains,):
+        raise RuntimeError(f"{name}: logw must be float64[{chains}]")
+    if u is None or u.dtype != torch.float64 or tuple(u.shape) != (groups,):
+        raise RuntimeError(f"{name}: u must be float64[{groups}]")
+    for t in (logw, u):
+        if t.device != x.device:
+            raise RuntimeError(f"{name}: all tensors must be on {x.device} (got one on {t.device})")
+    x_out = torch.empty_like(x)
+    ancestors = torch.empty(chains, dtype=torch.int32, device=x.device)
+    stats = torch.empty(groups, 4, dtype=torch.float64, device=x.device)
+    scratch = torch.empty(max(chains, 1), dtype=torch.float64, device=x.device)
+    call("mf_smc_resample", ptr(x), ptr(x_out), chains, d, groups, ptr(logw), ptr(u), float(ess_threshold), ptr(ancestors),
+         ptr(stats), ptr(scratch), stream_ptr(x))
+    return x_out, ancestors, stats
+
+
 def ment_logprob(x: torch.Tensor, desc: torch.Tensor, meta: torch.Tensor, tables: torch.Tensor, prior=(0, 0.0, 0.0),
                  want_grad: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """(logp[n], grad[n, d] or None) of mf_ment_logprob (include/mentflow_hip.h): the sum over slots of log clamp(h, 0, 1e10)

@@ -20,6 +20,9 @@ mentflow_amd/csrc/mala.hip).  Both derive from ``_ChainSampler``, which holds ev
 ``AnnealedImportanceSampler`` (no counterpart either) walks such Langevin chains along a temperature ladder from a normalised
 Gaussian to the MENT density and carries an importance weight per chain: the weights estimate the normaliser of the density
 (``MENT.log_normalization``), and the weighted final states, resampled, are draws from it (kernel in mentflow_amd/csrc/ais.hip).
+``SequentialMonteCarloSampler`` (no counterpart either) is that sampler with adaptive resampling per island on the way up the
+ladder (kernel in mentflow_amd/csrc/smc.hip) and a weighted population kept from call to call, which follows a density that
+changes a little by one reweighting step instead of a new ladder.
 """
 from __future__ import annotations
 
@@ -464,10 +467,8 @@ class AnnealedImportanceSampler:
         self.device = device
         return self
 
-    def run(self, ment) -> dict:
-        """Walk the whole ladder on `ment` and return ``x`` [chains, ndim] (the final states), ``logw`` [chains] float64 (the
-        log-weights), ``logp`` [chains] (``ment.log_density`` of the final states, as the kernel carries it) and ``accepted``
-        [chains] int32, all on the device.  No host synchronisation."""
+    def _prepare(self, ment):
+        """(kernel arguments of `ment`, device, base scale per axis): the checks every walk starts with."""
         from .ment import MENT
         from .prior import Gaussian
         name = type(self).__name__
@@ -483,30 +484,45 @@ class AnnealedImportanceSampler:
         base = self.base_scale
         if base is None:
             base = [float(ment.prior.scale)] * self.ndim if isinstance(ment.prior, Gaussian) else [1.0] * self.ndim
+        return args, device, base
+
+    def _start(self, device, base):
+        """(generator, x, logw, logp, accepted): exact draws of the base and what the chains carry."""
         gen = None
         if self.seed is not None:
             gen = torch.Generator(device=device)
             gen.manual_seed(self.seed)
-        d, chains, spt = self.ndim, self.chains, self.steps_per_temp
         mean_t = torch.tensor(self.base_mean, dtype=torch.float32, device=device)
         base_t = torch.tensor(base, dtype=torch.float32, device=device)
-        x = (mean_t + base_t * torch.randn(chains, d, device=device, generator=gen)).contiguous()
+        x = (mean_t + base_t * torch.randn(self.chains, self.ndim, device=device, generator=gen)).contiguous()
         _lib.ptr(x)                                            # the usual refusal of tensors the library does not compute on
-        betas = self.betas.to(device)
+        logw = torch.zeros(self.chains, dtype=torch.float64, device=device)
+        logp = torch.empty(self.chains, dtype=torch.float32, device=device)
+        accepted = torch.zeros(self.chains, dtype=torch.int32, device=device)
+        return gen, x, logw, logp, accepted
+
+    def _walk(self, args, base, gen, x, logw, logp, accepted, betas, spt: int, k_from: int, k_to: int) -> None:
+        """Temperatures k_from + 1 .. k_to of `betas` (on the device), in launches whose noise fits _AIS_NOISE_BYTES."""
+        d, chains, device = self.ndim, self.chains, x.device
         scale = torch.tensor(self.step, dtype=torch.float32, device=device)
-        logw = torch.zeros(chains, dtype=torch.float64, device=device)
-        logp = torch.empty(chains, dtype=torch.float32, device=device)
-        accepted = torch.zeros(chains, dtype=torch.int32, device=device)
         per = max(1, _AIS_NOISE_BYTES // (4 * (d + 1) * chains * max(1, spt)))
-        for k0 in range(0, self.n_temps, per):
-            k1 = min(self.n_temps, k0 + per)
+        for k0 in range(k_from, k_to, per):
+            k1 = min(k_to, k0 + per)
             nz = torch.empty((k1 - k0) * spt, d + 1, chains, device=device)
             for k in range(k1 - k0):                           # drawn per temperature: the stream does not depend on the cut
                 nz[k * spt:(k + 1) * spt, :d].normal_(generator=gen)
                 nz[k * spt:(k + 1) * spt, d].uniform_(generator=gen)
             ops.ais_ment_steps(x, args[0], args[1], args[2], args[3], nz, betas, spt, scale, self.base_mean, base, logw,
                                accepted, drift_clip=self.drift_clip, temp_offset=k0, ntemps=k1 - k0, logp=logp)
-        self.acceptance = accepted.sum().to(torch.float32) / float(max(1, self.n_temps * spt) * chains)
+
+    def run(self, ment) -> dict:
+        """Walk the whole ladder on `ment` and return ``x`` [chains, ndim] (the final states), ``logw`` [chains] float64 (the
+        log-weights), ``logp`` [chains] (``ment.log_density`` of the final states, as the kernel carries it) and ``accepted``
+        [chains] int32, all on the device.  No host synchronisation."""
+        args, device, base = self._prepare(ment)
+        gen, x, logw, logp, accepted = self._start(device, base)
+        self._walk(args, base, gen, x, logw, logp, accepted, self.betas.to(device), self.steps_per_temp, 0, self.n_temps)
+        self.acceptance = accepted.sum().to(torch.float32) / float(max(1, self.n_temps * self.steps_per_temp) * self.chains)
         self.last = dict(x=x, logw=logw, logp=logp, accepted=accepted)
         self._gen = gen
         return self.last
@@ -527,3 +543,154 @@ class AnnealedImportanceSampler:
         pos = (u + torch.arange(size, dtype=torch.float64, device=x.device)) * (cdf[-1] / size)
         idx = torch.searchsorted(cdf, pos, right=True).clamp_(max=self.chains - 1)
         return x[idx]
+
+
+class SequentialMonteCarloSampler(AnnealedImportanceSampler):
+    """A sequential Monte Carlo sampler on the density of a fully fused :class:`mentflow_amd.ment.MENT`: the chains, ladder and
+    weights of ``AnnealedImportanceSampler``, plus adaptive resampling on the way and a population that is kept across calls.
+
+    The `chains` states form `groups` independent islands of ``chains / groups`` consecutive chains.  The ladder is walked in
+    launches of ``resample_every`` temperatures; after every launch but the last, each island whose effective sample size has
+    fallen below ``ess_threshold`` times its size is resampled systematically from its own weights, with one uniform per
+    island, and its log-weights all become the island's log mean weight (kernel in mentflow_amd/csrc/smc.hip).  Every decision
+    is taken on the device: there is no host synchronisation.  Islands never exchange states, so the `groups` estimates
+    ``log_z_groups`` of log Z are independent and their spread is an honest standard error however often the chains were
+    resampled (``MENT.log_normalization``).  The noise of the moves is drawn as ``AnnealedImportanceSampler`` draws it and the
+    resampling uniforms come from a second generator (seeded ``(seed * 2654435761 + 1) mod 2^63``), so ``ess_threshold=0``
+    (no resampling launch at all) gives that class's ``run`` bit for bit.
+
+    ``sampler(prob_func, size)`` serves as ``MENT(sampler=...)``.  The first call (and every call with ``persistent=False``, or
+    after ``reset()``) walks the ladder.  Later calls bridge instead: the kept population is reweighted by the ratio of the new
+    density to the old one (``logw += log p_new(x) - log p_old(x)``, -inf where either side has no weight), resampled once
+    under ``ess_threshold`` and moved by ``bridge_steps`` Langevin transitions on the new density.  Between two Gauss-Seidel
+    sub-steps the density changes by a bounded factor in one table, which is one such step away.  In both cases the sample is
+    then collected: every island is resampled (which equalises its weights), and ``ceil(size / chains)`` rounds of ``thin``
+    transitions on the density each contribute the population.  ``last`` holds the latest dict (its ``logw`` are the weights
+    before that forced resampling), ``population`` the kept states with their weights and log-densities, and ``log_z`` the
+    running estimate ``logsumexp(log_z_groups) - log groups``, which follows the tables from call to call."""
+
+    def __init__(self, ndim: int, chains: int = 4096, n_temps: int = 64, steps_per_temp: int = 2,
+                 step: Union[float, Sequence[float]] = 0.25, drift_clip: float = 1.0, base_mean=None, base_scale=None,
+                 betas=None, seed: Optional[int] = None, device: torch.device = None, groups: int = 8,
+                 ess_threshold: float = 0.5, resample_every: int = 1, persistent: bool = True, bridge_steps: int = 4,
+                 thin: int = 2) -> None:
+        super().__init__(ndim, chains, n_temps, steps_per_temp, step, drift_clip, base_mean, base_scale, betas, seed, device)
+        name = type(self).__name__
+        self.groups = int(groups)
+        if self.groups < 1 or self.chains % self.groups != 0:
+            raise ValueError(f"{name}: groups >= 1 that divides chains expected (got {groups} for {self.chains} chains)")
+        self.ess_threshold = float(ess_threshold)
+        if not self.ess_threshold >= 0.0:
+            raise ValueError(f"{name}: ess_threshold >= 0 expected (got {ess_threshold})")
+        self.resample_every, self.bridge_steps, self.thin = int(resample_every), int(bridge_steps), int(thin)
+        if self.resample_every < 1 or self.bridge_steps < 0 or self.thin < 1:
+            raise ValueError(f"{name}: resample_every >= 1, bridge_steps >= 0 and thin >= 1 expected")
+        self.persistent = bool(persistent)
+        self.population: Optional[dict] = None           # x, logw, logp kept from the latest call
+        self.log_z: Optional[torch.Tensor] = None
+        self._gen_u: Optional[torch.Generator] = None    # the resampling uniforms' generator
+
+    def reset(self) -> None:
+        """Forget the population: the next call walks the whole ladder."""
+        self.population = None
+
+    def to(self, device):
+        self.device = device
+        if self.population is not None:
+            self.population = {k: v.to(device) for k, v in self.population.items()}
+        return self
+
+    # ---------------------------------------------------------------------------------------------------- internals
+    def _resample(self, x, logw, threshold: float):
+        """One resampling decision per island: (x, ancestors as int64, how many islands resampled); logw in place."""
+        u = torch.rand(self.groups, dtype=torch.float64, device=x.device, generator=self._gen_u)
+        x, ancestors, stats = ops.smc_resample(x, logw, u, self.groups, threshold)
+        return x, ancestors.long(), stats[:, 2].sum()
+
+    def _finish(self, x, logw, logp, accepted, resampled, transitions: int) -> dict:
+        per_island = logw.view(self.groups, -1)
+        lse = torch.logsumexp(per_island, 1)
+        wt = torch.exp(per_island - torch.where(torch.isneginf(lse), torch.zeros_like(lse), lse)[:, None])
+        ess = torch.where(torch.isneginf(lse), torch.zeros_like(lse), 1.0 / (wt * wt).sum(1).clamp_min(1e-300))
+        log_z_groups = lse - math.log(per_island.shape[1])
+        self.log_z = torch.logsumexp(log_z_groups, 0) - math.log(self.groups)
+        if transitions:
+            self.acceptance = accepted.sum().to(torch.float32) / float(transitions * self.chains)
+        self.last = dict(x=x, logw=logw, logp=logp, accepted=accepted, log_z_groups=log_z_groups, ess_groups=ess,
+                         resampled=resampled)
+        return self.last
+
+    def run(self, ment) -> dict:
+        """Walk the whole ladder on `ment` and return what ``AnnealedImportanceSampler.run`` returns (``x``, ``logw``,
+        ``logp``, ``accepted``) plus ``log_z_groups`` [groups] float64 (logsumexp of each island's log-weights minus the log
+        of its size), ``ess_groups`` [groups] (each island's effective sample size under its final weights) and ``resampled``
+        (0-dim: how many island resamplings took place), all on the device.  The final weights are not resampled, so they
+        stay informative for the entropy.  The kept population is not touched.  No host synchronisation."""
+        args, device, base = self._prepare(ment)
+        gen, x, logw, logp, accepted = self._start(device, base)
+        self._gen = gen
+        self._gen_u = None
+        if self.seed is not None:
+            self._gen_u = torch.Generator(device=device)
+            self._gen_u.manual_seed((self.seed * 2654435761 + 1) % (1 << 63))
+        betas = self.betas.to(device)
+        resampled = torch.zeros((), dtype=torch.float64, device=device)
+        for k0 in range(0, self.n_temps, self.resample_every):
+            k1 = min(self.n_temps, k0 + self.resample_every)
+            self._walk(args, base, gen, x, logw, logp, accepted, betas, self.steps_per_temp, k0, k1)
+            if k1 < self.n_temps and self.ess_threshold > 0.0:
+                x, ancestors, count = self._resample(x, logw, self.ess_threshold)
+                logp, accepted = logp[ancestors], accepted[ancestors]
+                resampled = resampled + count
+        return self._finish(x, logw, logp, accepted, resampled, self.n_temps * self.steps_per_temp)
+
+    def _at_target(self, args, base, x, logw, logp, accepted, steps: int) -> None:
+        """`steps` Langevin transitions on the density itself: the ladder [1, 1], whose weight increment is exactly 0."""
+        ones = torch.ones(2, dtype=torch.float32, device=x.device)
+        self._walk(args, base, self._gen, x, logw, logp, accepted, ones, steps, 0, 1)
+
+    def _bridge(self, ment) -> dict:
+        args, device, base = self._prepare(ment)
+        pop = self.population
+        x, logw, lp_old = pop["x"], pop["logw"].clone(), pop["logp"]
+        _lib.ptr(x)
+        lp_new = ops.ment_logprob(x, args[0], args[1], args[2], args[3])[0]
+        dead = torch.isneginf(logw) | torch.isneginf(lp_new) | torch.isneginf(lp_old)
+        zero = torch.zeros((), dtype=torch.float64, device=device)
+        inc = torch.where(dead, zero, lp_new.double()) - torch.where(dead, zero, lp_old.double())   # never inf - inf
+        logw = torch.where(dead, torch.full_like(logw, float("-inf")), logw + inc)
+        logp = lp_new
+        accepted = torch.zeros(self.chains, dtype=torch.int32, device=device)
+        resampled = torch.zeros((), dtype=torch.float64, device=device)
+        if self.ess_threshold > 0.0:
+            x, ancestors, resampled = self._resample(x, logw, self.ess_threshold)
+            logp = logp[ancestors]
+        else:
+            x = x.clone()
+        if self.bridge_steps:
+            self._at_target(args, base, x, logw, logp, accepted, self.bridge_steps)
+        return self._finish(x, logw, logp, accepted, resampled, self.bridge_steps)
+
+    def __call__(self, prob_func: Callable, size: int) -> torch.Tensor:
+        from .ment import MENT
+        owner = getattr(prob_func, "__self__", None)
+        if not isinstance(owner, MENT) or getattr(prob_func, "__func__", None) is not MENT.prob:
+            raise NotImplementedError(f"{type(self).__name__} takes the bound MENT.prob of a MENT (got "
+                                      f"{getattr(prob_func, '__qualname__', prob_func)}): there is no generic path")
+        size = int(size)
+        if not self.persistent:
+            self.reset()
+        res = self.run(owner) if self.population is None else self._bridge(owner)
+        args, device, base = self._prepare(owner)
+        # a forced resampling of every island equalises the weights; then rounds of moves on the density, each kept
+        logw = res["logw"].clone()
+        x, ancestors, _ = self._resample(res["x"], logw, 2.0)
+        logp = res["logp"][ancestors]
+        accepted = torch.zeros(self.chains, dtype=torch.int32, device=device)
+        rounds = max(1, math.ceil(size / self.chains))
+        out = torch.empty(rounds, self.chains, self.ndim, device=device)
+        for r in range(rounds):
+            self._at_target(args, base, x, logw, logp, accepted, self.thin)
+            out[r] = x
+        self.population = dict(x=x, logw=logw, logp=logp)
+        return out.reshape(-1, self.ndim)[:size]

@@ -1,0 +1,15 @@
+"""The sequential-Monte-Carlo section of the sanitizer driver (tests/emu/sanitize_smc.cpp): mf_smc_resample of
+mentflow_amd/csrc/smc.hip on the host build with AddressSanitizer + UndefinedBehaviorSanitizer, on buffers of exactly the
+documented sizes (islands of 1 and of a ragged 257 chains, an island whose weights are all -inf, 3 islands among them).  It is part
+of the same stand-alone binary as every other section (tests/test_sanitizers.py builds it); this module runs that binary and looks
+for the section's own marker."""
+import subprocess
+
+from test_sanitizers import ENV, sanitize_binary  # noqa: F401  (the fixture builds tests/emu/sanitize_emu when it is out of date)
+
+
+def test_smc_section_is_clean_under_asan_and_ubsan(sanitize_binary):  # noqa: F811
+    r = subprocess.run([sanitize_binary], env=ENV, capture_output=True, text=True, timeout=1500)
+    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+    assert "SANITIZE SMC OK" in r.stdout
+    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr
