@@ -1,6 +1,7 @@
-// What the chain samplers on classical MENT's density (mcmc.hip, mala.hip) have in common: one lane per chain, the noise layout
-// [steps][d + 1][chains], which steps are kept and where they go.  The transition rules are in the two files.  The helpers take
-// any argument struct with the fields of ChainArgs: MalaArgs keeps a field order of its own (see mala.hip).
+// What the chain samplers on classical MENT's density (mcmc.hip, mala.hip, ais.hip) have in common: one lane per chain, the noise
+// layout [steps][d + 1][chains], which steps are kept and where they go.  The random walk's rule is in mcmc.hip, the Langevin
+// transition of the other two is stated in ment_langevin.h.  The helpers take any argument struct with the fields of ChainArgs:
+// MalaArgs (mala.hip) and AisArgs (ais.hip) keep a field order of their own.
 #pragma once
 #include "ment_slots.h"
 
@@ -37,7 +38,7 @@ __device__ __forceinline__ void chain_keep(const Args& ca, int64_t t, int c, con
     ++keep_row;
 }
 
-// checks the chain arguments of entry point `who` ("mcmc", "mala": the prefix of its messages) and fills the ChainArgs
+// checks the chain arguments of entry point `who` ("mcmc", "mala", "ais": the prefix of its messages) and fills the ChainArgs
 // fields of *ca
 template <class Args>
 static int chain_args(const char* who, int64_t chains, int d, const float* noise, int64_t steps, int64_t step_offset,

@@ -635,9 +635,18 @@ def ment_integrate(minv: torch.Tensor, coords: List[torch.Tensor], meas_axes, de
     return pred
 
 
+def _check_slots(name: str, desc, meta) -> int:
+    """The shape check of the slot descriptors that every MENT entry point taking them shares; returns nslot."""
+    nslot = desc.shape[0]
+    if desc.dtype != _F32 or tuple(desc.shape) != (nslot, MENT_DESC) or meta.dtype != torch.int32 or tuple(meta.shape) != (nslot, 4):
+        raise RuntimeError(f"{name}: desc float32[nslot, {MENT_DESC}] and meta int32[nslot, 4] expected (got "
+                           f"{desc.dtype}{tuple(desc.shape)}, {meta.dtype}{tuple(meta.shape)})")
+    return nslot
+
+
 def _check_chain_steps(name: str, x, desc, meta, tables, noise, scale, accepted, step_offset, keep_from, keep_every, out,
                        extra=()) -> Tuple[int, int, int, int, int, int]:
-    """The argument checks that mcmc_ment_steps and mala_ment_steps share; `name` opens the messages.  Returns
+    """The argument checks that mcmc_ment_steps, mala_ment_steps and ais_ment_steps share; `name` opens the messages.  Returns
     (chains, d, steps, step_offset, keep_from, keep_every)."""
     if x.dim() != 2 or not 1 <= x.shape[1] <= 8:
         raise RuntimeError(f"{name}: x[chains, d <= 8] expected (got {tuple(x.shape)})")
@@ -651,10 +660,7 @@ def _check_chain_steps(name: str, x, desc, meta, tables, noise, scale, accepted,
         raise RuntimeError(f"{name}: noise[steps, {d + 1}, {chains}] expected (got {tuple(noise.shape)})")
     if tuple(scale.shape) != (d,):
         raise RuntimeError(f"{name}: scale[{d}] expected (got {tuple(scale.shape)})")
-    nslot = desc.shape[0]
-    if desc.dtype != _F32 or tuple(desc.shape) != (nslot, MENT_DESC) or meta.dtype != torch.int32 or tuple(meta.shape) != (nslot, 4):
-        raise RuntimeError(f"{name}: desc float32[nslot, {MENT_DESC}] and meta int32[nslot, 4] expected (got "
-                           f"{desc.dtype}{tuple(desc.shape)}, {meta.dtype}{tuple(meta.shape)})")
+    _check_slots(name, desc, meta)
     steps = noise.shape[0]
     step_offset, keep_from, keep_every = int(step_offset), int(keep_from), int(keep_every)
     if step_offset < 0 or keep_from < 0 or keep_every < 1:
@@ -685,6 +691,16 @@ def mcmc_ment_steps(x: torch.Tensor, desc: torch.Tensor, meta: torch.Tensor, tab
          ptr(out), ptr(accepted), stream_ptr(x))
 
 
+def _check_langevin(name: str, chains: int, drift_clip, logp) -> float:
+    """What mala_ment_steps and ais_ment_steps check on top of _check_chain_steps; returns drift_clip as a float."""
+    drift_clip = float(drift_clip)
+    if not drift_clip >= 0.0:
+        raise RuntimeError(f"{name}: drift_clip >= 0 expected (got {drift_clip})")
+    if logp is not None and (logp.dtype != _F32 or tuple(logp.shape) != (chains,)):
+        raise RuntimeError(f"{name}: logp must be float32[{chains}] (got {logp.dtype}{tuple(logp.shape)})")
+    return drift_clip
+
+
 def mala_ment_steps(x: torch.Tensor, desc: torch.Tensor, meta: torch.Tensor, tables: torch.Tensor, prior, noise: torch.Tensor,
                     scale: torch.Tensor, accepted: torch.Tensor, drift_clip: float = 1.0, step_offset: int = 0,
                     keep_from: int = 0, keep_every: int = 1, out: Optional[torch.Tensor] = None,
@@ -695,11 +711,7 @@ def mala_ment_steps(x: torch.Tensor, desc: torch.Tensor, meta: torch.Tensor, tab
     log-density of the final states."""
     chains, d, steps, step_offset, keep_from, keep_every = _check_chain_steps(
         "mala_ment_steps", x, desc, meta, tables, noise, scale, accepted, step_offset, keep_from, keep_every, out, extra=(logp,))
-    drift_clip = float(drift_clip)
-    if not drift_clip >= 0.0:
-        raise RuntimeError(f"mala_ment_steps: drift_clip >= 0 expected (got {drift_clip})")
-    if logp is not None and (logp.dtype != _F32 or tuple(logp.shape) != (chains,)):
-        raise RuntimeError(f"mala_ment_steps: logp must be float32[{chains}] (got {logp.dtype}{tuple(logp.shape)})")
+    drift_clip = _check_langevin("mala_ment_steps", chains, drift_clip, logp)
     call("mf_mala_ment_steps", ptr(x), chains, d, desc.shape[0], ptr(desc), ptr(meta), ptr(tables), tables.numel(),
          int(prior[0]), float(prior[1]), float(prior[2]), ptr(noise), steps, step_offset, ptr(scale), drift_clip, keep_from,
          keep_every, ptr(out), ptr(accepted), ptr(logp), stream_ptr(x))
@@ -728,11 +740,7 @@ def ais_ment_steps(x: torch.Tensor, desc: torch.Tensor, meta: torch.Tensor, tabl
         raise RuntimeError(f"{name}: noise[{ntemps * steps_per_temp}, d + 1, chains] expected (got {tuple(noise.shape)})")
     chains, d = _check_chain_steps(name, x, desc, meta, tables, noise, scale, accepted, temp_offset * steps_per_temp, 0, 1, out,
                                    extra=(logp, logw, betas))[:2]
-    drift_clip = float(drift_clip)
-    if not drift_clip >= 0.0:
-        raise RuntimeError(f"{name}: drift_clip >= 0 expected (got {drift_clip})")
-    if logp is not None and (logp.dtype != _F32 or tuple(logp.shape) != (chains,)):
-        raise RuntimeError(f"{name}: logp must be float32[{chains}] (got {logp.dtype}{tuple(logp.shape)})")
+    drift_clip = _check_langevin(name, chains, drift_clip, logp)
     if logw is None or logw.dtype != torch.float64 or tuple(logw.shape) != (chains,):
         raise RuntimeError(f"{name}: logw must be float64[{chains}]")
     mean, base = [float(v) for v in base_mean], [float(v) for v in base_scale]
@@ -786,10 +794,7 @@ def ment_logprob(x: torch.Tensor, desc: torch.Tensor, meta: torch.Tensor, tables
     if x.dim() != 2 or not 1 <= x.shape[1] <= 8:
         raise RuntimeError(f"ment_logprob: x[n, d <= 8] expected (got {tuple(x.shape)})")
     x, tables = _f32c(x), _f32c(tables)
-    nslot = desc.shape[0]
-    if desc.dtype != _F32 or tuple(desc.shape) != (nslot, MENT_DESC) or meta.dtype != torch.int32 or tuple(meta.shape) != (nslot, 4):
-        raise RuntimeError(f"ment_logprob: desc float32[nslot, {MENT_DESC}] and meta int32[nslot, 4] expected (got "
-                           f"{desc.dtype}{tuple(desc.shape)}, {meta.dtype}{tuple(meta.shape)})")
+    nslot = _check_slots("ment_logprob", desc, meta)
     for t in (desc, meta, tables):
         if t.device != x.device:
             raise RuntimeError(f"ment_logprob: all tensors must be on {x.device} (got one on {t.device})")
@@ -813,10 +818,7 @@ def ment_logprob_table_grad(x: torch.Tensor, desc: torch.Tensor, meta: torch.Ten
         raise RuntimeError(f"ment_logprob_table_grad: x[n, d <= 8] expected (got {tuple(x.shape)})")
     x, tables, logp, weight = _f32c(x), _f32c(tables), _f32c(logp), _f32c(weight)
     n, d = x.shape
-    nslot = desc.shape[0]
-    if desc.dtype != _F32 or tuple(desc.shape) != (nslot, MENT_DESC) or meta.dtype != torch.int32 or tuple(meta.shape) != (nslot, 4):
-        raise RuntimeError(f"ment_logprob_table_grad: desc float32[nslot, {MENT_DESC}] and meta int32[nslot, 4] expected (got "
-                           f"{desc.dtype}{tuple(desc.shape)}, {meta.dtype}{tuple(meta.shape)})")
+    nslot = _check_slots("ment_logprob_table_grad", desc, meta)
     if tuple(logp.shape) != (n,) or tuple(weight.shape) != (n,):
         raise RuntimeError(f"ment_logprob_table_grad: logp[{n}] and weight[{n}] expected (got {tuple(logp.shape)}, "
                            f"{tuple(weight.shape)})")

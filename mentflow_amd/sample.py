@@ -70,6 +70,50 @@ def sample_hist(hist: torch.Tensor, edges: List[torch.Tensor], size: int, noise:
     return torch.squeeze(x)
 
 
+def _ment_of(prob_func: Callable, required_by: Optional[str] = None):
+    """The MENT whose own ``MENT.prob`` (not ``log_prob``, not a subclass's override) `prob_func` is bound to, else None: the one
+    density the fused kernels compute.  With `required_by` (a sampler without a generic path) None is refused instead."""
+    from .ment import MENT
+    owner = getattr(prob_func, "__self__", None)
+    if isinstance(owner, MENT) and getattr(prob_func, "__func__", None) is MENT.prob:
+        return owner
+    if required_by is not None:
+        raise NotImplementedError(f"{required_by} takes the bound MENT.prob of a MENT (got "
+                                  f"{getattr(prob_func, '__qualname__', prob_func)}): there is no generic path")
+    return None
+
+
+def _per_axis(name: str, ndim: int, value, default: float, what: str) -> List[float]:
+    if value is None:
+        return [default] * ndim
+    if isinstance(value, (int, float)):
+        return [float(value)] * ndim
+    out = [float(v) for v in value]
+    if len(out) != ndim:
+        raise ValueError(f"{name}: {what} must be a float or {ndim} per-axis values (got {len(out)})")
+    return out
+
+
+def _check_axes(name: str, ndim: int, step, bad_step: Optional[str] = None) -> Tuple[int, List[float]]:
+    """(ndim, step per axis) of a chain sampler, validated.  bad_step: AnnealedImportanceSampler's wording of a refused step."""
+    ndim = int(ndim)
+    if not 1 <= ndim <= 8:
+        raise ValueError(f"{name}: 1 <= ndim <= 8 expected (got {ndim})")
+    steps = [float(step)] * ndim if isinstance(step, (int, float)) else [float(v) for v in step]
+    if len(steps) != ndim:
+        raise ValueError(bad_step or f"{name}: step must be a float or {ndim} per-axis scales (got {len(steps)})")
+    return ndim, steps
+
+
+def _check_drift(name: str, steps: List[float], drift_clip: float, bad_step: Optional[str] = None) -> float:
+    """What a Langevin transition needs on top of _check_axes: step > 0 on every axis and drift_clip >= 0, which is returned."""
+    if not all(v > 0 for v in steps):
+        raise ValueError(bad_step or f"{name}: step > 0 expected on every axis (got {steps})")
+    if not float(drift_clip) >= 0.0:
+        raise ValueError(f"{name}: drift_clip >= 0 expected (got {drift_clip})")
+    return float(drift_clip)
+
+
 class GridSampler:
     """sample.py:59-113."""
 
@@ -98,13 +142,9 @@ class GridSampler:
         return points
 
     def __call__(self, prob_func: Callable, size: int) -> torch.Tensor:
-        from .ment import MENT
-        # the implicit-grid kernel computes exactly MENT.prob: taken for that method only (not for log_prob, nor for a
-        # subclass that overrides prob), else the density handed in is evaluated on the stored points
-        owner = getattr(prob_func, "__self__", None)
-        fused = None
-        if isinstance(owner, MENT) and getattr(prob_func, "__func__", None) is MENT.prob:
-            fused = owner.prob_on_grid(self.coords)
+        # the implicit-grid kernel computes exactly MENT.prob, else the density handed in is evaluated on the stored points
+        owner = _ment_of(prob_func)
+        fused = owner.prob_on_grid(self.coords) if owner is not None else None
         if fused is None:                                      # any density: evaluate it on the stored grid points
             prob = torch.reshape(prob_func(self.get_grid_points()), tuple(self.shape))
             return self.send(sample_hist(prob, self.edges, size=size, noise=self.noise, device=self.device))
@@ -138,14 +178,10 @@ class _ChainSampler:
                  start: Optional[torch.Tensor], start_scale: float, persistent: bool, burn_persistent: Optional[int],
                  device: torch.device) -> None:
         name = type(self).__name__
-        self.ndim, self.chains = int(ndim), int(chains)
-        if not 1 <= self.ndim <= 8:
-            raise ValueError(f"{name}: 1 <= ndim <= 8 expected (got {ndim})")
+        self.ndim, self.step = _check_axes(name, ndim, step)
+        self.chains = int(chains)
         if self.chains < 1 or int(burn) < 0 or int(thin) < 1:
             raise ValueError(f"{name}: chains >= 1, burn >= 0 and thin >= 1 expected")
-        self.step = [float(step)] * self.ndim if isinstance(step, (int, float)) else [float(v) for v in step]
-        if len(self.step) != self.ndim:
-            raise ValueError(f"{name}: step must be a float or {self.ndim} per-axis scales (got {len(self.step)})")
         if start is not None and tuple(start.shape) != (self.chains, self.ndim):
             raise ValueError(f"{name}: start[{self.chains}, {self.ndim}] expected (got {tuple(start.shape)})")
         self.burn, self.thin = int(burn), int(thin)
@@ -171,13 +207,12 @@ class _ChainSampler:
 
     # ---------------------------------------------------------------------------------------------------- internals
     def _fused_args(self, prob_func: Callable):
-        from .ment import MENT
-        owner = getattr(prob_func, "__self__", None)
-        if isinstance(owner, MENT) and getattr(prob_func, "__func__", None) is MENT.prob:
-            if owner.ndim != self.ndim:
-                raise ValueError(f"{type(self).__name__}(ndim={self.ndim}) called with the density of a MENT of ndim={owner.ndim}")
-            return owner.fused_args()
-        return None
+        owner = _ment_of(prob_func)
+        if owner is None:
+            return None
+        if owner.ndim != self.ndim:
+            raise ValueError(f"{type(self).__name__}(ndim={self.ndim}) called with the density of a MENT of ndim={owner.ndim}")
+        return owner.fused_args()
 
     def _init_state(self, prob_func: Callable) -> None:
         device = self.device
@@ -326,11 +361,7 @@ class LangevinSampler(_ChainSampler):
                  burn_persistent: Optional[int] = None, device: torch.device = None, drift_clip: float = 1.0,
                  log_density: Optional[Callable] = None) -> None:
         super().__init__(ndim, chains, step, burn, thin, start, start_scale, persistent, burn_persistent, device)
-        if not all(v > 0 for v in self.step):
-            raise ValueError(f"LangevinSampler: step > 0 expected on every axis (got {self.step})")
-        self.drift_clip = float(drift_clip)
-        if not self.drift_clip >= 0.0:
-            raise ValueError(f"LangevinSampler: drift_clip >= 0 expected (got {drift_clip})")
+        self.drift_clip = _check_drift(type(self).__name__, self.step, drift_clip)
         self.log_density = log_density
 
     def _target(self, prob_func: Callable, fused) -> Optional[Callable]:
@@ -339,6 +370,7 @@ class LangevinSampler(_ChainSampler):
             return None
         if self.log_density is not None:
             return self.log_density
+        # not _ment_of: log_density also serves a subclass's own prob, which the kernels do not compute, if the subclass says so
         owner = getattr(prob_func, "__self__", None)
         if isinstance(owner, MENT) and getattr(prob_func, "__func__", None) is type(owner).prob:
             # a subclass that overrides prob alone has a density that MENT.log_density does not describe
@@ -423,17 +455,12 @@ class AnnealedImportanceSampler:
                  step: Union[float, Sequence[float]] = 0.25, drift_clip: float = 1.0, base_mean=None, base_scale=None,
                  betas=None, seed: Optional[int] = None, device: torch.device = None) -> None:
         name = type(self).__name__
-        self.ndim, self.chains, self.steps_per_temp = int(ndim), int(chains), int(steps_per_temp)
-        if not 1 <= self.ndim <= 8:
-            raise ValueError(f"{name}: 1 <= ndim <= 8 expected (got {ndim})")
+        bad_step = f"{name}: step must be a positive float or {int(ndim)} positive per-axis scales (got {step})"
+        self.ndim, self.step = _check_axes(name, ndim, step, bad_step)
+        self.drift_clip = _check_drift(name, self.step, drift_clip, bad_step)
+        self.chains, self.steps_per_temp = int(chains), int(steps_per_temp)
         if self.chains < 1 or self.steps_per_temp < 0:
             raise ValueError(f"{name}: chains >= 1 and steps_per_temp >= 0 expected")
-        self.step = [float(step)] * self.ndim if isinstance(step, (int, float)) else [float(v) for v in step]
-        if len(self.step) != self.ndim or not all(v > 0 for v in self.step):
-            raise ValueError(f"{name}: step must be a positive float or {self.ndim} positive per-axis scales (got {step})")
-        self.drift_clip = float(drift_clip)
-        if not self.drift_clip >= 0.0:
-            raise ValueError(f"{name}: drift_clip >= 0 expected (got {drift_clip})")
         if betas is None:
             if int(n_temps) < 1:
                 raise ValueError(f"{name}: n_temps >= 1 expected (got {n_temps})")
@@ -443,8 +470,8 @@ class AnnealedImportanceSampler:
             raise ValueError(f"{name}: betas must start at 0, end at 1 and not decrease")
         self.betas = betas
         self.n_temps = betas.numel() - 1
-        self.base_mean = self._per_axis(base_mean, 0.0, "base_mean")
-        self.base_scale = None if base_scale is None else self._per_axis(base_scale, 1.0, "base_scale")
+        self.base_mean = _per_axis(name, self.ndim, base_mean, 0.0, "base_mean")
+        self.base_scale = None if base_scale is None else _per_axis(name, self.ndim, base_scale, 1.0, "base_scale")
         if self.base_scale is not None and not all(0.0 < b < math.inf for b in self.base_scale):
             raise ValueError(f"{name}: base_scale > 0 expected on every axis (got {self.base_scale})")
         self.seed = None if seed is None else int(seed)
@@ -452,16 +479,6 @@ class AnnealedImportanceSampler:
         self.acceptance: Optional[torch.Tensor] = None
         self.last: Optional[dict] = None                 # what the latest run returned
         self._gen: Optional[torch.Generator] = None      # the latest run's generator: __call__ draws its one uniform from it
-
-    def _per_axis(self, value, default: float, what: str) -> List[float]:
-        if value is None:
-            return [default] * self.ndim
-        if isinstance(value, (int, float)):
-            return [float(value)] * self.ndim
-        out = [float(v) for v in value]
-        if len(out) != self.ndim:
-            raise ValueError(f"{type(self).__name__}: {what} must be a float or {self.ndim} per-axis values (got {len(out)})")
-        return out
 
     def to(self, device):
         self.device = device
@@ -528,11 +545,7 @@ class AnnealedImportanceSampler:
         return self.last
 
     def __call__(self, prob_func: Callable, size: int) -> torch.Tensor:
-        from .ment import MENT
-        owner = getattr(prob_func, "__self__", None)
-        if not isinstance(owner, MENT) or getattr(prob_func, "__func__", None) is not MENT.prob:
-            raise NotImplementedError(f"{type(self).__name__} takes the bound MENT.prob of a MENT (got "
-                                      f"{getattr(prob_func, '__qualname__', prob_func)}): there is no generic path")
+        owner = _ment_of(prob_func, required_by=type(self).__name__)
         res = self.run(owner)
         x, logw = res["x"], res["logw"]
         size = int(size)
@@ -672,11 +685,7 @@ class SequentialMonteCarloSampler(AnnealedImportanceSampler):
         return self._finish(x, logw, logp, accepted, resampled, self.bridge_steps)
 
     def __call__(self, prob_func: Callable, size: int) -> torch.Tensor:
-        from .ment import MENT
-        owner = getattr(prob_func, "__self__", None)
-        if not isinstance(owner, MENT) or getattr(prob_func, "__func__", None) is not MENT.prob:
-            raise NotImplementedError(f"{type(self).__name__} takes the bound MENT.prob of a MENT (got "
-                                      f"{getattr(prob_func, '__qualname__', prob_func)}): there is no generic path")
+        owner = _ment_of(prob_func, required_by=type(self).__name__)
         size = int(size)
         if not self.persistent:
             self.reset()

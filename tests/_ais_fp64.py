@@ -4,7 +4,8 @@ _mala_fp64.verify generalised to a temperature per transition.
 With lp, g the MENT log-density and its gradient, the base q0 = N(m, diag b^2) with lq(x) = c0 - 0.5 sum ((x_j - m_j) / b_j)^2 and
 gq_j = -(x_j - m_j) / b_j^2, the tempered density at temperature B is
     l_B = B > 0 ? lq + B (lp - lq) : lq,        g_B = l_B == -inf ? 0 : (B > 0 ? gq + B (g - gq) : gq),
-and a transition is mala.hip's with l -> l_B and g -> g_B (mentflow_amd/csrc/ais.hip).  Every transition is judged from the
+and a transition is mala.hip's with l -> l_B and g -> g_B (mentflow_amd/csrc/ment_langevin.h, ais.hip), so _mala_fp64.verify
+judges it, given below what stands in the place of l, g, the band and the clamp error.  Every transition is judged from the
 sampler's OWN previous state (the `out` rows of ops.ais_ment_steps), so an fp32 chain and the fp64 yardstick cannot drift apart.
 
 Proposal.  The kernel and mf_ment_logprob call one device function, so the fp32 lp32 and g32 that ops.ment_logprob returns for x
@@ -26,9 +27,8 @@ import math
 
 import torch
 
-from _mala_fp64 import TOL, _near_hull, assert_transitions  # noqa: F401  (assert_transitions is re-exported)
-from _mcmc_fp64 import _ulp32
-from _ment_logp_fp64 import logp64
+from _mala_fp64 import TOL, assert_transitions  # noqa: F401  (assert_transitions is re-exported)
+from _mala_fp64 import verify as _mala_verify
 
 EPS = 2.0e-6
 
@@ -78,63 +78,44 @@ def _temper64(beta, l, g, lq, gq):
     return lb, torch.where(torch.isneginf(lb)[:, None], torch.zeros_like(gb), gb)
 
 
-def _drift_edge(gb, err, a, c):
-    """The unclamped drift a g_B lies within the gradient error of the clamp +-c (never with c == 0)."""
-    return (((a * gb).abs() - c).abs() <= a * err[:, None]).logical_and(c > 0).any(1)
+class _Tempered:
+    """The `base` of _mala_fp64.verify: what the tempered target puts in the place of the plain one's l and g, and of its band and
+    clamp errors.  betas [T]: the temperature of each transition; mean, base_scale: d floats."""
+
+    def __init__(self, betas, mean, base_scale):
+        self.betas, self.mean, self.base_scale = betas, mean, base_scale
+
+    def per_transition(self, T, C):
+        assert tuple(self.betas.shape) == (T,)
+        return self.betas.float().cpu()[:, None].expand(T, C).reshape(T * C).contiguous()
+
+    def grad32(self, b32, x, lp32, g32):
+        """g_B at x from the backend's own fp32 value and gradient, in the kernel's operation order."""
+        lq32, gq32 = base32(x, self.mean, self.base_scale)
+        return temper32(b32, lp32.float().cpu(), g32.float().cpu(), lq32, gq32)[1]
+
+    def target64(self, b32, x, y, lx, gx, ly, gy):
+        """(l_B, g_B, l, g, lq, gq) at x and at y."""
+        B = b32.double()
+        lqx, gqx = _base64(x, self.mean, self.base_scale)
+        lqy, gqy = _base64(y, self.mean, self.base_scale)
+        lbx, gbx = _temper64(B, lx, gx, lqx, gqx)
+        lby, gby = _temper64(B, torch.nan_to_num(ly, nan=0.0, neginf=float("-inf")), torch.nan_to_num(gy), lqy, gqy)
+        return (lbx, gbx, lx, gx, lqx, gqx), (lby, gby, ly, gy, lqy, gqy)
+
+    def errors(self, b32, tx, ty, rs):
+        """(band, gradient error at x, at y) from what target64 returned and rs = sum_j |r_j| 0.5 s_j."""
+        B = b32.double()
+        (_, _, lx, gx, lqx, gqx), (_, _, ly, gy, lqy, gqy) = tx, ty
+        gy_inf, gqy_inf = torch.nan_to_num(gy).abs().amax(1), gqy.abs().amax(1)
+        lmag = torch.where(B > 0, lx.abs() + torch.nan_to_num(ly, nan=0.0).abs(), torch.zeros_like(B))    # at B == 0 lp plays no part
+        band = B * (TOL * (2 + lmag) + rs * TOL * (1 + gy_inf)) + EPS * ((2 + lqx.abs() + lqy.abs() + B * lmag) + rs * (1 + gqy_inf))
+        err_x = B * TOL * (1 + gx.abs().amax(1)) + EPS * (1 + gqx.abs().amax(1))
+        return band, err_x, B * TOL * (1 + gy_inf) + EPS * (1 + gqy_inf)
 
 
 def verify(start, noise, traj, betas, scale, drift_clip, slots, prior64, logp32, mean, base_scale):
     """start [C, d], noise [T, d + 1, C], traj [T, C, d] (the state after every transition), betas [T] (the temperature of
     each transition), scale [d] or float; logp32(x [n, d]) -> (lp32 [n], g32 [n, d]) of mf_ment_logprob at x on the backend
     under test (CPU tensors); mean, base_scale: d floats.  Returns _mala_fp64.verify's dict of counts."""
-    start, noise, traj = start.detach().cpu(), noise.detach().cpu(), traj.detach().cpu()
-    T, C, d = traj.shape
-    assert tuple(noise.shape) == (T, d + 1, C) and tuple(start.shape) == (C, d) and tuple(betas.shape) == (T,)
-    s32 = torch.as_tensor(scale, dtype=torch.float32).cpu().reshape(-1).expand(d).contiguous()
-    prev = torch.cat([start[None], traj[:-1]]).reshape(T * C, d)
-    nxt = traj.reshape(T * C, d)
-    z = noise[:, :d].permute(0, 2, 1).reshape(T * C, d)
-    u = noise[:, d].reshape(T * C)
-    b32 = betas.float().cpu()[:, None].expand(T, C).reshape(T * C).contiguous()
-    n = prev.shape[0]
-    # the proposal, from the backend's own fp32 value and gradient, in the kernel's operation order
-    a32, c32 = (0.5 * s32) * s32, torch.tensor(float(drift_clip), dtype=torch.float32) * s32
-    lp32, g32 = logp32(prev.contiguous())
-    lq32, gq32 = base32(prev, mean, base_scale)
-    _, gb32 = temper32(b32, lp32.float().cpu(), g32.float().cpu(), lq32, gq32)
-    base = prev + torch.minimum(torch.maximum(a32 * gb32, -c32), c32)
-    y = s32.double() * z.double() + base.double()
-    nan = torch.isnan(y).any(1) | torch.isnan(u)
-    y_clean = torch.where(nan[:, None], torch.zeros_like(y), y)
-    # the decision in fp64
-    s, a, c, B = s32.double(), a32.double(), c32.double(), b32.double()
-    lx, gx, _ = logp64(prev, slots, prior64)
-    ly, gy, amb_y = logp64(y_clean, slots, prior64)
-    nan |= torch.isnan(ly)
-    lqx, gqx = _base64(prev, mean, base_scale)
-    lqy, gqy = _base64(y_clean, mean, base_scale)
-    lbx, gbx = _temper64(B, lx, gx, lqx, gqx)
-    lby, gby = _temper64(B, torch.nan_to_num(ly, nan=0.0, neginf=float("-inf")), torch.nan_to_num(gy), lqy, gqy)
-    r = ((prev.double() - y_clean) - torch.minimum(torch.maximum(a * gby, -c), c)) / s
-    delta = (lby - lbx) + 0.5 * ((z.double() ** 2).sum(1) - (r ** 2).sum(1))
-    gy_inf, gqy_inf = torch.nan_to_num(gy).abs().amax(1), gqy.abs().amax(1)
-    rs = (r.abs() * 0.5 * s).sum(1)
-    lmag = torch.where(B > 0, lx.abs() + torch.nan_to_num(ly, nan=0.0).abs(), torch.zeros_like(B))    # at B == 0 lp plays no part
-    band = B * (TOL * (2 + lmag) + rs * TOL * (1 + gy_inf)) + EPS * ((2 + lqx.abs() + lqy.abs() + B * lmag) + rs * (1 + gqy_inf))
-    log_u = torch.log(u.double())
-    x_out, y_in = torch.isneginf(lbx), lby > float("-inf")
-    must_accept = torch.where(y_in, x_out | (log_u < delta - band), x_out)
-    must_reject = torch.where(y_in, ~x_out & (log_u > delta + band), ~x_out)
-    err_x = B * TOL * (1 + gx.abs().amax(1)) + EPS * (1 + gqx.abs().amax(1))
-    err_y = B * TOL * (1 + gy_inf) + EPS * (1 + gqy_inf)
-    edge = _near_hull(prev, slots) | amb_y | _drift_edge(gbx, err_x, a, c) | _drift_edge(gby, err_y, a, c)
-    must_accept &= ~edge & ~nan
-    must_reject = (must_reject & ~edge) | nan
-    in_band = y_in & ~x_out & ~nan & ~(log_u < delta - band) & ~(log_u > delta + band)
-    stayed = (nxt.view(torch.int32) == prev.view(torch.int32)).all(1)
-    moved_to_y = ((nxt.double() - y).abs() <= 2 * _ulp32(y)).all(1)
-    in_band &= ~edge
-    return dict(total=n, ambiguous=int((~must_accept & ~must_reject).sum()), in_band=int(in_band.sum()),
-                must_accept=int(must_accept.sum()),
-                accept_wrong=int((must_accept & ~moved_to_y).sum()), reject_wrong=int((must_reject & ~stayed).sum()),
-                malformed=int((~stayed & ~moved_to_y).sum()), accepted=int((~stayed).sum()))
+    return _mala_verify(start, noise, traj, scale, drift_clip, slots, prior64, logp32, base=_Tempered(betas, mean, base_scale))

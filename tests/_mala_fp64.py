@@ -23,7 +23,11 @@ gradient; the first term is that value error of l(x) and l(y), the second the gr
                 a 3e-4 (1 + |g64|_inf) of +-c (fp32 and fp64 may clamp differently).
 x at an INTERIOR bin centre is not ambiguous, which makes the verifier stricter than flagging every point logp64 flags: log p is
 continuous there, so the cell fp32 picks changes l(x) by no more than the rounding of any other point, and the one-sided
-derivative it picks is not compared at all, since the proposal is rebuilt from the backend's own fp32 gradient."""
+derivative it picks is not compared at all, since the proposal is rebuilt from the backend's own fp32 gradient.
+
+The transition is the one of mentflow_amd/csrc/ment_langevin.h, which ais.hip restates on a tempered target: `verify` judges that
+one too when it is given a `base` (tests/_ais_fp64.py, which states what the base adds to the band and to the clamp test).
+Without a base nothing of it is evaluated: no factor 1 and no term 0 enters the plain target's arithmetic."""
 import torch
 
 from _mcmc_fp64 import _ulp32
@@ -43,19 +47,21 @@ def _near_hull(x, slots):
     return near
 
 
-def _drift_edge(g, a, c):
-    """The unclamped drift a g lies within the gradient error of the clamp +-c (never with c == 0: the drift is 0 either way)."""
-    err = a * TOL * (1 + g.abs().amax(1, keepdim=True))
+def _drift_edge(g, err, c, a):
+    """The unclamped drift a g lies within err, the gradient error times a, of the clamp +-c (never with c == 0: the drift is 0
+    either way)."""
     return (((a * g).abs() - c).abs() <= err).logical_and(c > 0).any(1)
 
 
-def verify(start, noise, traj, scale, drift_clip, slots, prior64, grad32, pick=None):
+def verify(start, noise, traj, scale, drift_clip, slots, prior64, grad32, pick=None, base=None):
     """start [C, d], noise [T, d + 1, C], traj [T, C, d] (the state after every step), scale [d] or float; grad32(x [n, d]) ->
     the fp32 gradient of mf_ment_logprob at x on the backend under test (CPU tensor); pick: indices into the T * C transitions
-    to judge (default all).  Returns a dict of counts."""
+    to judge (default all); base: None, or the tempered target of _ais_fp64 (then grad32 returns (lp32, g32)).  Returns a dict
+    of counts."""
     start, noise, traj = start.detach().cpu(), noise.detach().cpu(), traj.detach().cpu()
     T, C, d = traj.shape
     assert tuple(noise.shape) == (T, d + 1, C) and tuple(start.shape) == (C, d)
+    b32 = None if base is None else base.per_transition(T, C)
     s32 = torch.as_tensor(scale, dtype=torch.float32).cpu().reshape(-1).expand(d).contiguous()
     prev = torch.cat([start[None], traj[:-1]]).reshape(T * C, d)
     nxt = traj.reshape(T * C, d)
@@ -63,12 +69,13 @@ def verify(start, noise, traj, scale, drift_clip, slots, prior64, grad32, pick=N
     u = noise[:, d].reshape(T * C)
     if pick is not None:
         prev, nxt, z, u = prev[pick], nxt[pick], z[pick], u[pick]
+        b32 = None if base is None else b32[pick]
     n = prev.shape[0]
     # the proposal, from the backend's own fp32 gradient, in the kernel's operation order
     a32, c32 = (0.5 * s32) * s32, torch.tensor(float(drift_clip), dtype=torch.float32) * s32
-    g32 = grad32(prev.contiguous()).float().cpu()
-    base = prev + torch.minimum(torch.maximum(a32 * g32, -c32), c32)
-    y = s32.double() * z.double() + base.double()
+    g32 = grad32(prev.contiguous())
+    g32 = g32.float().cpu() if base is None else base.grad32(b32, prev, *g32)
+    y = s32.double() * z.double() + (prev + torch.minimum(torch.maximum(a32 * g32, -c32), c32)).double()
     nan = torch.isnan(y).any(1) | torch.isnan(u)
     y_clean = torch.where(nan[:, None], torch.zeros_like(y), y)
     # the decision in fp64
@@ -76,14 +83,24 @@ def verify(start, noise, traj, scale, drift_clip, slots, prior64, grad32, pick=N
     lx, gx, _ = logp64(prev, slots, prior64)
     ly, gy, amb_y = logp64(y_clean, slots, prior64)
     nan |= torch.isnan(ly)
+    if base is not None:                                   # the target's value and gradient: l_B and g_B for l and g
+        tx, ty = base.target64(b32, prev, y_clean, lx, gx, ly, gy)
+        (lx, gx), (ly, gy) = tx[:2], ty[:2]
     r = ((prev.double() - y_clean) - torch.minimum(torch.maximum(a * gy, -c), c)) / s
     delta = (ly - lx) + 0.5 * ((z.double() ** 2).sum(1) - (r ** 2).sum(1))
-    band = TOL * (2 + lx.abs() + ly.abs()) + (r.abs() * 0.5 * s).sum(1) * TOL * (1 + gy.abs().amax(1))
+    rs = (r.abs() * 0.5 * s).sum(1)
+    if base is None:
+        band = TOL * (2 + lx.abs() + ly.abs()) + rs * TOL * (1 + gy.abs().amax(1))
+        err_x = a * TOL * (1 + gx.abs().amax(1, keepdim=True))
+        err_y = a * TOL * (1 + torch.nan_to_num(gy).abs().amax(1, keepdim=True))
+    else:
+        band, err_x, err_y = base.errors(b32, tx, ty, rs)
+        err_x, err_y = a * err_x[:, None], a * err_y[:, None]
     log_u = torch.log(u.double())
     x_out, y_in = torch.isneginf(lx), ly > float("-inf")
     must_accept = torch.where(y_in, x_out | (log_u < delta - band), x_out)
     must_reject = torch.where(y_in, ~x_out & (log_u > delta + band), ~x_out)
-    edge = _near_hull(prev, slots) | amb_y | _drift_edge(gx, a, c) | _drift_edge(torch.nan_to_num(gy), a, c)
+    edge = _near_hull(prev, slots) | amb_y | _drift_edge(gx, err_x, c, a) | _drift_edge(torch.nan_to_num(gy), err_y, c, a)
     must_accept &= ~edge & ~nan
     must_reject = (must_reject & ~edge) | nan
     in_band = y_in & ~x_out & ~nan & ~(log_u < delta - band) & ~(log_u > delta + band)
