@@ -6,12 +6,16 @@ ground-truth samples, as experiments/rec_nd_1d/setup.py::setup_eval does.  `--sa
 Metropolis-Hastings chains (mentflow_amd.sample.MetropolisHastingsSampler) instead of the dense grid, `--sampler mala` from
 Metropolis-adjusted Langevin chains (mentflow_amd.sample.LangevinSampler), whose proposals follow the gradient of the log-density,
 `--sampler smc` from a sequential Monte Carlo population (mentflow_amd.sample.SequentialMonteCarloSampler): a temperature ladder
-with resampling per island at the first sub-step, one reweighting step per later sub-step, and a running estimate of log Z.
+with resampling per island at the first sub-step, one reweighting step per later sub-step, and a running estimate of log Z,
+`--sampler ais` from annealed importance sampling (mentflow_amd.sample.AnnealedImportanceSampler).  With `--weighted` (ais and smc
+only) every sub-step bins the sampler's `--chains` states with their importance weights instead of `--samples` rows resampled
+from them (model.weighted = True).
 
     python examples/train_ment_nd_1d.py [--epochs 5] [--num 50] [--res 33]
     python examples/train_ment_nd_1d.py --sampler mh [--chains 65536] [--step 0.25] [--burn 200] [--thin 10]
     python examples/train_ment_nd_1d.py --sampler mala [--drift-clip 1.0] [--chains 65536] [--step 0.25] [--burn 200] [--thin 10]
     python examples/train_ment_nd_1d.py --sampler smc [--chains 65536] [--step 0.25] [--temps 32] [--groups 8] [--ess-threshold 0.5]
+    python examples/train_ment_nd_1d.py --sampler ais|smc --weighted [--chains 65536] [--temps 32]
 """
 import argparse
 import os
@@ -25,8 +29,8 @@ import mentflow_amd as mf  # noqa: E402
 from mentflow_amd.distributions import get_distribution  # noqa: E402
 from mentflow_amd.harness import build_problem  # noqa: E402
 from mentflow_amd.ment import MENT  # noqa: E402
-from mentflow_amd.sample import (GridSampler, LangevinSampler, MetropolisHastingsSampler,  # noqa: E402
-                                 SequentialMonteCarloSampler)
+from mentflow_amd.sample import (AnnealedImportanceSampler, GridSampler, LangevinSampler,  # noqa: E402
+                                 MetropolisHastingsSampler, SequentialMonteCarloSampler)
 from mentflow_amd.train import MENTTrainer  # noqa: E402
 
 
@@ -38,7 +42,7 @@ def main():
     ap.add_argument("--res", type=int, default=33)
     ap.add_argument("--samples", type=int, default=1_000_000)
     ap.add_argument("--eval-size", type=int, default=50_000)
-    ap.add_argument("--sampler", choices=("grid", "mh", "mala", "smc"), default="grid")
+    ap.add_argument("--sampler", choices=("grid", "mh", "mala", "smc", "ais"), default="grid")
     ap.add_argument("--chains", type=int, default=65536)
     ap.add_argument("--step", type=float, default=0.25)
     ap.add_argument("--burn", type=int, default=200)
@@ -47,7 +51,11 @@ def main():
     ap.add_argument("--temps", type=int, default=32, help="smc: temperatures of the ladder")
     ap.add_argument("--groups", type=int, default=8, help="smc: independent islands")
     ap.add_argument("--ess-threshold", type=float, default=0.5, help="smc: an island resamples below this share of its size")
+    ap.add_argument("--weighted", action="store_true",
+                    help="ais, smc: bin the sampler's weighted states as they are instead of resampling --samples rows from them")
     args = ap.parse_args()
+    if args.weighted and args.sampler not in ("ais", "smc"):
+        ap.error(f"--weighted needs a sampler that carries weights (--sampler ais or smc), not {args.sampler}")
     dev = torch.device("cuda", 0)
     ndim, xmax = 4, 4.0
     prob = build_problem(ndim=ndim, num=args.num, bins=args.bins, xmax=xmax, seed=2, dist_name="gaussian_mixture",
@@ -60,12 +68,16 @@ def main():
     elif args.sampler == "smc":
         sampler = SequentialMonteCarloSampler(ndim, chains=args.chains, step=args.step, n_temps=args.temps, groups=args.groups,
                                               ess_threshold=args.ess_threshold, drift_clip=args.drift_clip)
+    elif args.sampler == "ais":
+        sampler = AnnealedImportanceSampler(ndim, chains=args.chains, step=args.step, n_temps=args.temps,
+                                            drift_clip=args.drift_clip)
     else:               # chains started inside the support: a chain that starts outside it walks freely and may not return
         sampler = MetropolisHastingsSampler(ndim, chains=args.chains, step=args.step, burn=args.burn, thin=args.thin,
                                             start_scale=0.5)
     model = MENT(ndim=ndim, transforms=prob.transforms, diagnostics=prob.diagnostics, measurements=prob.measurements,
                  prior=mf.prior.Gaussian(ndim=ndim, scale=3.0), mode="sample", sampler=sampler.to(dev),
                  n_samples=args.samples, device=dev)
+    model.weighted = args.weighted
 
     # the ground truth of build_problem (same name, ndim and seed), drawn afresh at every evaluation
     evaluate = mf.Evaluator(args.eval_size, distance=mf.loss.SlicedWassersteinDistance(n_projections=50, p=2, device=dev),

@@ -243,6 +243,38 @@ int mf_proj_hist2d_counts(const float* x, int64_t n, int d, const float* V0, con
                           void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Weighted projection histograms (mentflow_amd/csrc/wproj.hip): the entry points above for particles with a weight each.
+ *   w[n]:    one fp32 weight per row.  A weight that is not finite and positive (0, negative, NaN, +-inf) contributes
+ *            nothing to S or sums and gets gx = 0.
+ *   wmax[1]: DEVICE scalar, the largest valid weight (0 if there is none: S is then all zero).  The forwards accumulate
+ *            (w_n / wmax) K in the 2^-50 fixed point of the unweighted kernels and multiply wmax back in at the end, so a
+ *            contribution below 2^-50 * wmax rounds to zero.  Sums stay exact integers: order independent, bitwise
+ *            reproducible; all weights 1 give the unweighted result bit for bit.
+ *   S[p,k]   = sum_n w_n K_npk                    ws: mf_proj_kde_ws_bytes(P, bins) bytes, as above
+ *   gx[n,d] (+)= w_n * (gx of the unweighted backward);   gw[n] (+)= sum_p sum_k gS[p,k] K_npk for a weight that is valid
+ *            or zero, 0 for a negative, NaN or infinite one.  Either of gx, gw may be NULL (not wanted), not both.
+ *   sums[p,k] = sum of w_n over the rows whose projection lies in bin k: torch.histogram(weight=...) semantics, bins as
+ *            mf_proj_hist{1,2}d_counts (out of range ignored, last bin right-inclusive); fp32, ws as for the KDE forwards.
+ * Launch shapes are those of the unweighted entry point of the same sizes (mf_proj_kde_plan).  Every entry point refuses
+ * null pointers, d outside 1..8, fewer than 2 bins, P < 1, P * bins >= 2^31, a sigma that is not finite and positive and
+ * a 2-D radius outside 0..5, with the reason in mf_last_error().  Purely additive: MF_ABI_VERSION stays 5.            */
+int mf_proj_wkde1d_fwd(const float* x, const float* w, const float* wmax, int64_t n, int d, const float* V, int P,
+                       const float* coords, int B, float sigma, int radius, float* S, void* ws, void* stream);
+int mf_proj_wkde1d_bwd(const float* x, const float* w, int64_t n, int d, const float* V, int P, const float* coords, int B,
+                       float sigma, int radius, const float* gS, float* gx, float* gw, int accumulate, void* stream);
+int mf_proj_wkde2d_fwd(const float* x, const float* w, const float* wmax, int64_t n, int d, const float* V0,
+                       const float* V1, int P, const float* coords_x, int Bx, float sigma_x, int radius_x,
+                       const float* coords_y, int By, float sigma_y, int radius_y, float* S, void* ws, void* stream);
+int mf_proj_wkde2d_bwd(const float* x, const float* w, int64_t n, int d, const float* V0, const float* V1, int P,
+                       const float* coords_x, int Bx, float sigma_x, int radius_x, const float* coords_y, int By,
+                       float sigma_y, int radius_y, const float* gS, float* gx, float* gw, int accumulate, void* stream);
+int mf_proj_whist1d_sums(const float* x, const float* w, const float* wmax, int64_t n, int d, const float* V, int P,
+                         const float* edges, int B, float* sums, void* ws, void* stream);
+int mf_proj_whist2d_sums(const float* x, const float* w, const float* wmax, int64_t n, int d, const float* V0,
+                         const float* V1, int P, const float* edges_x, int Bx, const float* edges_y, int By, float* sums,
+                         void* ws, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Histogram normalisation + discrepancy for P projections (tiny: P*bins elements; one workgroup per projection).
  *   normalize != 0:  prob = S * pre_scale   (1-D: pre_scale = 1/N_total, histogram.py:39;  2-D: 1, histogram.py:69)
  *                    ghat = prob / (sum(prob) * cell + eps)                        (histogram.py:40-43,70-73)

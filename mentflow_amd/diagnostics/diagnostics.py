@@ -61,16 +61,32 @@ def _dense_chunk_2d(x, V0, V1, cx, cy, sx, sy):
     return torch.einsum("npa,npb->pab", _gauss(x @ V0.T, cx, sx), _gauss(x @ V1.T, cy, sy))
 
 
-def _dense_sums(fn, x: torch.Tensor, per_particle: int, *args) -> torch.Tensor:
+def _dense_chunk_1d_w(x, w, V, c, sigma):
+    return (_gauss(x @ V.T, c, sigma) * w[:, None, None]).sum(0)
+
+
+def _dense_chunk_2d_w(x, w, V0, V1, cx, cy, sx, sy):
+    return torch.einsum("n,npa,npb->pab", w, _gauss(x @ V0.T, cx, sx), _gauss(x @ V1.T, cy, sy))
+
+
+def _dense_sums(fn, x: torch.Tensor, per_particle: int, *args, weights: Optional[torch.Tensor] = None) -> torch.Tensor:
     """sum over particle chunks of fn(x_chunk, *args): each chunk is recomputed in the backward (checkpoint), so neither
-    pass holds more than one chunk's kernel matrix."""
+    pass holds more than one chunk's kernel matrix.  With weights, fn(x_chunk, w_chunk, *args)."""
     chunk = max(1, _DENSE_CHUNK_ELEMS // max(1, per_particle))
     total = None
     for a in range(0, x.shape[0], chunk):
         xc = x[a:a + chunk]
-        part = checkpoint(fn, xc, *args, use_reentrant=False) if xc.requires_grad else fn(xc, *args)
+        head = (xc,) if weights is None else (xc, weights[a:a + chunk])
+        grad = any(t.requires_grad for t in head)
+        part = checkpoint(fn, *head, *args, use_reentrant=False) if grad else fn(*head, *args)
         total = part if total is None else total + part
     return total
+
+
+def weight_total(weights: torch.Tensor) -> torch.Tensor:
+    """W = the sum of the valid weights as a device scalar (1 where there is none: the sums are all zero then)."""
+    W = ops.valid_weights(weights).sum()
+    return torch.where(W > 0, W, torch.ones_like(W))
 
 
 class Diagnostic(torch.nn.Module):
@@ -117,10 +133,12 @@ class Histogram(Diagnostic):
     # particles at hand (kernel sums for kde=True, bin counts otherwise), from_sums(S, n) finishes [P, bins...] histograms from
     # sums over n particles.  batched = from_sums(raw_sums); a data-parallel run all-reduces the sums in between
     # (MENTFlow.loss, simulate.raw_sums).
-    def raw_sums(self, x: torch.Tensor, rows: List[torch.Tensor]) -> torch.Tensor:
+    # weights [n] (optional, everywhere): one weight per particle; the sums become weighted sums and n is replaced by W, the
+    # sum of the valid weights (finite and positive; any other weight counts as 0).  Differentiable in the weights for kde=True.
+    def raw_sums(self, x: torch.Tensor, rows: List[torch.Tensor], weights: Optional[torch.Tensor] = None) -> torch.Tensor:
         raise NotImplementedError
 
-    def from_sums(self, S: torch.Tensor, n_total: int) -> torch.Tensor:
+    def from_sums(self, S: torch.Tensor, n_total: int, weights: Optional[torch.Tensor] = None) -> torch.Tensor:
         raise NotImplementedError
 
     uniform = True              # every axis on a uniform grid: the KDE kernels apply (set by the subclasses)
@@ -135,12 +153,14 @@ class Histogram(Diagnostic):
         eye = torch.eye(x.shape[1], dtype=x.dtype, device=x.device)
         return [r[None, :] for r in self.projection_rows(eye)]
 
-    def batched(self, x: torch.Tensor, rows: List[torch.Tensor]) -> torch.Tensor:
+    def batched(self, x: torch.Tensor, rows: List[torch.Tensor], weights: Optional[torch.Tensor] = None) -> torch.Tensor:
         """All P projections in one launch: [P, bins...] normalised histograms (kde) or densities (hard bins)."""
-        return self.from_sums(self.raw_sums(x, rows), x.shape[0])
+        if weights is None:
+            return self.from_sums(self.raw_sums(x, rows), x.shape[0])
+        return self.from_sums(self.raw_sums(x, rows, weights), x.shape[0], weights)
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        return self._apply_noise(self.batched(x, self.identity_rows(x))[0])
+    def forward(self, x: torch.Tensor, weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+        return self._apply_noise(self.batched(x, self.identity_rows(x), weights)[0])
 
 
 class Histogram1D(Histogram):
@@ -182,17 +202,27 @@ class Histogram1D(Histogram):
             return [matrix[self.axis]]
         return [self.direction.to(matrix) @ matrix]
 
-    def raw_sums(self, x: torch.Tensor, rows: List[torch.Tensor]) -> torch.Tensor:
+    def raw_sums(self, x: torch.Tensor, rows: List[torch.Tensor], weights: Optional[torch.Tensor] = None) -> torch.Tensor:
         V = rows[0].to(torch.float32).contiguous()
         if self.kde and not self.uniform:
             self._log_dense()
+            if weights is not None:
+                return _dense_sums(_dense_chunk_1d_w, x, V.shape[0] * self.coords.numel(), V.to(x), self.coords.to(x),
+                                   self.bandwidth_value, weights=ops.valid_weights(weights).to(x))
             return _dense_sums(_dense_chunk_1d, x, V.shape[0] * self.coords.numel(), V.to(x), self.coords.to(x),
                                self.bandwidth_value)
+        if self.kde and weights is not None:
+            return ops.ProjWKde1dFn.apply(x, weights, V, self.coords, self.bandwidth_value, ops.kde_radius(self.bandwidth_bins))
         if self.kde:
             return ops.ProjKde1dFn.apply(x, V, self.coords, self.bandwidth_value, ops.kde_radius(self.bandwidth_bins))
+        if weights is not None:
+            return ops.proj_whist_sums_1d(x.detach(), weights.detach(), V, self.edges)
         return ops.proj_hist_counts_1d(x.detach(), V, self.edges).to(torch.float32)
 
-    def from_sums(self, S: torch.Tensor, n_total: int) -> torch.Tensor:
+    def from_sums(self, S: torch.Tensor, n_total: int, weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if self.kde and weights is not None:            # (S / W) / (delta * sum_k S_k / W + 1e-10): n replaced by W
+            ghat, _ = ops.HistNormDiscFn.apply(S / weight_total(weights), None, True, 1.0, self.cell_value, 1.0e-10, 0, 0.0, 1.0)
+            return ghat
         if self.kde:
             ghat, _ = ops.HistNormDiscFn.apply(S, None, True, 1.0 / n_total, self.cell_value, 1.0e-10, 0, 0.0, 1.0)
             return ghat
@@ -244,21 +274,33 @@ class Histogram2D(Histogram):
     def projection_rows(self, matrix: torch.Tensor) -> List[torch.Tensor]:
         return [matrix[self.axis[0]], matrix[self.axis[1]]]
 
-    def raw_sums(self, x: torch.Tensor, rows: List[torch.Tensor]) -> torch.Tensor:
+    def raw_sums(self, x: torch.Tensor, rows: List[torch.Tensor], weights: Optional[torch.Tensor] = None) -> torch.Tensor:
         V0 = rows[0].to(torch.float32).contiguous()
         V1 = rows[1].to(torch.float32).contiguous()
         if self.kde and not self.uniform:
             self._log_dense()
+            if weights is not None:
+                return _dense_sums(_dense_chunk_2d_w, x, V0.shape[0] * (self.coords_x.numel() + self.coords_y.numel()
+                                                                        + self.coords_x.numel() * self.coords_y.numel()),
+                                   V0.to(x), V1.to(x), self.coords_x.to(x), self.coords_y.to(x), *self.bandwidth_values,
+                                   weights=ops.valid_weights(weights).to(x))
             return _dense_sums(_dense_chunk_2d, x, V0.shape[0] * (self.coords_x.numel() + self.coords_y.numel()
                                                                   + self.coords_x.numel() * self.coords_y.numel()),
                                V0.to(x), V1.to(x), self.coords_x.to(x), self.coords_y.to(x), *self.bandwidth_values)
+        if self.kde and weights is not None:
+            return ops.ProjWKde2dFn.apply(x, weights, V0, V1, self.coords_x, self.coords_y, self.bandwidth_values[0],
+                                          self.bandwidth_values[1], ops.kde_radius(self.bandwidth_bins[0]),
+                                          ops.kde_radius(self.bandwidth_bins[1]))
         if self.kde:
             return ops.ProjKde2dFn.apply(x, V0, V1, self.coords_x, self.coords_y, self.bandwidth_values[0],
                                          self.bandwidth_values[1], ops.kde_radius(self.bandwidth_bins[0]),
                                          ops.kde_radius(self.bandwidth_bins[1]))
+        if weights is not None:
+            return ops.proj_whist_sums_2d(x.detach(), weights.detach(), V0, V1, self.edges_x, self.edges_y)
         return ops.proj_hist_counts_2d(x.detach(), V0, V1, self.edges_x, self.edges_y).to(torch.float32)
 
-    def from_sums(self, S: torch.Tensor, n_total: int) -> torch.Tensor:
+    def from_sums(self, S: torch.Tensor, n_total: int, weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+        # (the 2-D normalisation S / (dx dy sum S + 1e-10) never divides by n, so the weights change nothing here)
         if self.kde:
             P, Bx, By = S.shape
             ghat, _ = ops.HistNormDiscFn.apply(S.reshape(P, Bx * By), None, True, 1.0,

@@ -33,7 +33,7 @@ from typing import Any, Callable, List, Optional, Tuple
 import torch
 
 from . import ops
-from .diagnostics import Histogram1D, Histogram2D
+from .diagnostics import Histogram, Histogram1D, Histogram2D
 from .loss import kl_divergence
 from .prior import Gaussian
 from .simulate import forward
@@ -213,10 +213,31 @@ class MENT:
         self.integration_limits = integration_limits
         self.integration_shape = integration_shape
         self.sampler = sampler
+        self._weighted = False                                # see the `weighted` property
         self.n_samples = int(n_samples)
         self.interpolation = interpolation
         self.lagrange_functions = self.initialize_lagrange_functions()
         self.log_z: Optional[torch.Tensor] = None            # log of the normaliser, once log_normalization has estimated it
+
+    @property
+    def weighted(self) -> bool:
+        """Sample mode with particle weights: when set, a simulation takes the sampler's states with their importance weights
+        (``sampler.sample_weighted``) and bins them as they are, instead of ``n_samples`` equal-weight rows resampled from them.
+        An attribute, set after construction (the constructor keeps the reference's signature); setting it with a sampler
+        that has no ``sample_weighted`` raises ``TypeError``, and so does a simulation after ``sampler`` was replaced by one
+        that has none."""
+        return self._weighted
+
+    @weighted.setter
+    def weighted(self, value: bool) -> None:
+        if value:
+            self._check_weighted_sampler()
+        self._weighted = bool(value)
+
+    def _check_weighted_sampler(self) -> None:
+        if not callable(getattr(self.sampler, "sample_weighted", None)):
+            raise TypeError(f"MENT.weighted needs a sampler with sample_weighted (AnnealedImportanceSampler, "
+                            f"SequentialMonteCarloSampler); got {type(self.sampler).__name__}")
 
     def send(self, x):
         return x.type(torch.float32).to(self.device)
@@ -536,6 +557,15 @@ class MENT:
     def sample(self, size: int) -> torch.Tensor:
         return self.send(self.sampler(self.prob, size))
 
+    def _sample_for_simulation(self) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """(x, weights) of one sample-mode simulation: n_samples equal-weight rows (weights None), or with `weighted` the
+        sampler's own states and their weights."""
+        if not self.weighted:
+            return self.send(self.sample(int(self.n_samples))), None
+        self._check_weighted_sampler()                        # the sampler may have been replaced since the flag was set
+        x, w = self.sampler.sample_weighted(self.prob, int(self.n_samples))
+        return self.send(x), self.send(w)
+
     def sample_and_log_prob(self, size: int) -> Tuple[torch.Tensor, torch.Tensor]:
         x = self.sample(size)
         return x, self.log_prob(x)
@@ -583,16 +613,21 @@ class MENT:
         return self.normalize_projection(self.send(prediction), index, diag_index)
 
     def _simulate_sample(self, index: int, diag_index: int) -> torch.Tensor:
-        x = self.send(self.sample(int(self.n_samples)))
+        x, weights = self._sample_for_simulation()
         diagnostic = self.diagnostics[index][diag_index]
         prediction = None
         for chain in self._get_plan()[0]:
             if (index, diag_index) in chain.slots:
                 rows = chain.rows[chain.slots.index((index, diag_index))]
                 xin = apply_pre(x, chain.pre) if chain.pre else x
-                prediction = diagnostic._apply_noise(diagnostic.batched(xin, [r[None, :].to(x) for r in rows])[0])
+                prediction = diagnostic._apply_noise(diagnostic.batched(xin, [r[None, :].to(x) for r in rows], weights)[0])
         if prediction is None:
-            prediction = diagnostic(self.transforms[index](x))
+            if weights is not None and not isinstance(diagnostic, Histogram):
+                raise NotImplementedError(
+                    f"weighted simulation: {type(diagnostic).__name__} (measurement [{index}][{diag_index}]) takes no particle "
+                    "weights; histogram diagnostics do (Histogram1D / Histogram2D)")
+            u = self.transforms[index](x)
+            prediction = diagnostic(u) if weights is None else diagnostic(u, weights)
         return self.normalize_projection(prediction, index, diag_index)
 
     def simulate(self, index: int, diag_index: int, **kws) -> torch.Tensor:
@@ -626,15 +661,15 @@ class MENT:
             for index in range(len(self.transforms)):
                 predictions.append([self._simulate_integrate(index, j, **kws) for j in range(len(self.diagnostics[index]))])
         elif self.mode == "sample":
-            x = self.send(self.sample(self.n_samples))
-            predictions = forward(x, self.transforms, self.diagnostics)
+            x, weights = self._sample_for_simulation()
+            predictions = forward(x, self.transforms, self.diagnostics, weights)
         return predictions
 
     # ---------------------------------------------------------------------------------------------------- state
     def save(self, path: str) -> None:
         state = {"lagrange_functions": self.lagrange_functions, "epoch": self.epoch, "transforms": self.transforms,
                  "diagnostics": self.diagnostics, "measurements": self.measurements, "prior": self.prior,
-                 "ndim": self.ndim, "sampler": self.sampler}
+                 "ndim": self.ndim, "sampler": self.sampler, "weighted": self.weighted}
         torch.save(state, path)
 
     def load(self, path: str, device: torch.device = None) -> None:
@@ -647,6 +682,7 @@ class MENT:
         self.prior = state["prior"]
         self.ndim = state["ndim"]
         self.sampler = state["sampler"]
+        self.weighted = bool(state.get("weighted", False))     # after the sampler: the setter checks it
         self._plan = None
         self.to(device)
 

@@ -360,6 +360,115 @@ class ProjKde2dFn(torch.autograd.Function):
         return gx, None, None, None, None, None, None, None, None
 
 
+# ------------------------------------------------------------------------------------------------ weighted projections
+def valid_weights(w: torch.Tensor) -> torch.Tensor:
+    """w with every negative, NaN or infinite weight replaced by 0: what the weighted kernels count.  A zero weight passes
+    through, so that it keeps its gradient."""
+    return torch.where(torch.isfinite(w) & (w >= 0), w, torch.zeros_like(w))
+
+
+def weight_max(w: torch.Tensor) -> torch.Tensor:
+    """[1] device scalar: the largest valid weight, 0 if there is none.  Torch reductions only: no host synchronisation."""
+    if w.numel() == 0:
+        return torch.zeros(1, dtype=_F32, device=w.device)
+    return valid_weights(w).amax().reshape(1)
+
+
+def _check_weights(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    w = _f32c(w)
+    if w.dim() != 1 or w.shape[0] != x.shape[0] or w.device != x.device:
+        raise ValueError(f"weights must be a [{x.shape[0]}] tensor on {x.device} (got {tuple(w.shape)} on {w.device})")
+    return w
+
+
+class ProjWKde1dFn(torch.autograd.Function):
+    """x[N,d], w[N], V[P,d] -> S[P,B] = sum_n w_n exp(-((x_n.V_p - c_k)/sigma)^2 / 2); differentiable in x and w
+    (mf_proj_wkde1d_fwd / _bwd: one backward launch for both gradients, skipped per input by needs_input_grad)."""
+
+    @staticmethod
+    def forward(ctx, x, w, V, coords, sigma: float, radius: int):
+        x, V, coords = _f32c(x), _f32c(V), _f32c(coords)
+        w = _check_weights(x, w)
+        P, B = V.shape[0], coords.numel()
+        S = torch.empty(P, B, dtype=_F32, device=x.device)
+        ws = torch.empty(_lib.get_lib().mf_proj_kde_ws_bytes(P, B) // 8, dtype=torch.int64, device=x.device)
+        wmax = weight_max(w)
+        call("mf_proj_wkde1d_fwd", ptr(x), ptr(w), ptr(wmax), x.shape[0], x.shape[1], ptr(V), P, ptr(coords), B, float(sigma),
+             int(radius), ptr(S), ptr(ws), stream_ptr(x))
+        ctx.save_for_backward(x, w, V, coords)
+        ctx.sigma, ctx.radius = float(sigma), int(radius)
+        return S
+
+    @staticmethod
+    def backward(ctx, gS):
+        x, w, V, coords = ctx.saved_tensors
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_x or need_w):
+            return None, None, None, None, None, None
+        gx = torch.empty_like(x) if need_x else None
+        gw = torch.empty_like(w) if need_w else None
+        call("mf_proj_wkde1d_bwd", ptr(x), ptr(w), x.shape[0], x.shape[1], ptr(V), V.shape[0], ptr(coords), coords.numel(),
+             ctx.sigma, ctx.radius, ptr(_f32c(gS)), ptr(gx), ptr(gw), 0, stream_ptr(x))
+        return gx, gw, None, None, None, None
+
+
+class ProjWKde2dFn(torch.autograd.Function):
+    """x[N,d], w[N], V0[P,d], V1[P,d] -> S[P,Bx,By] = sum_n w_n Kx_na Ky_nb; differentiable in x and w."""
+
+    @staticmethod
+    def forward(ctx, x, w, V0, V1, coords_x, coords_y, sigma_x: float, sigma_y: float, radius_x: int, radius_y: int):
+        x, V0, V1, cx, cy = _f32c(x), _f32c(V0), _f32c(V1), _f32c(coords_x), _f32c(coords_y)
+        w = _check_weights(x, w)
+        P, Bx, By = V0.shape[0], cx.numel(), cy.numel()
+        S = torch.empty(P, Bx, By, dtype=_F32, device=x.device)
+        ws = torch.empty(_lib.get_lib().mf_proj_kde_ws_bytes(P, Bx * By) // 8, dtype=torch.int64, device=x.device)
+        wmax = weight_max(w)
+        call("mf_proj_wkde2d_fwd", ptr(x), ptr(w), ptr(wmax), x.shape[0], x.shape[1], ptr(V0), ptr(V1), P, ptr(cx), Bx,
+             float(sigma_x), int(radius_x), ptr(cy), By, float(sigma_y), int(radius_y), ptr(S), ptr(ws), stream_ptr(x))
+        ctx.save_for_backward(x, w, V0, V1, cx, cy)
+        ctx.args = (float(sigma_x), float(sigma_y), int(radius_x), int(radius_y))
+        return S
+
+    @staticmethod
+    def backward(ctx, gS):
+        x, w, V0, V1, cx, cy = ctx.saved_tensors
+        sx, sy, rx, ry = ctx.args
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_x or need_w):
+            return (None,) * 10
+        gx = torch.empty_like(x) if need_x else None
+        gw = torch.empty_like(w) if need_w else None
+        call("mf_proj_wkde2d_bwd", ptr(x), ptr(w), x.shape[0], x.shape[1], ptr(V0), ptr(V1), V0.shape[0], ptr(cx), cx.numel(),
+             sx, rx, ptr(cy), cy.numel(), sy, ry, ptr(_f32c(gS)), ptr(gx), ptr(gw), 0, stream_ptr(x))
+        return (gx, gw) + (None,) * 8
+
+
+def proj_whist_sums_1d(x, w, V, edges) -> torch.Tensor:
+    """[P,B] fp32 sums of w over the rows whose projection x.V_p lies in each bin (torch.histogram(weight=w) semantics)."""
+    x, V, edges = _f32c(x), _f32c(V), _f32c(edges)
+    w = _check_weights(x, w)
+    P, B = V.shape[0], edges.numel() - 1
+    sums = torch.empty(P, B, dtype=_F32, device=x.device)
+    ws = torch.empty(_lib.get_lib().mf_proj_kde_ws_bytes(P, B) // 8, dtype=torch.int64, device=x.device)
+    wmax = weight_max(w)
+    call("mf_proj_whist1d_sums", ptr(x), ptr(w), ptr(wmax), x.shape[0], x.shape[1], ptr(V), P, ptr(edges), B, ptr(sums),
+         ptr(ws), stream_ptr(x))
+    return sums
+
+
+def proj_whist_sums_2d(x, w, V0, V1, edges_x, edges_y) -> torch.Tensor:
+    """[P,Bx,By] fp32 sums of w per cell (np.histogramdd(weights=w) semantics)."""
+    x, V0, V1, ex, ey = _f32c(x), _f32c(V0), _f32c(V1), _f32c(edges_x), _f32c(edges_y)
+    w = _check_weights(x, w)
+    P, Bx, By = V0.shape[0], ex.numel() - 1, ey.numel() - 1
+    sums = torch.empty(P, Bx, By, dtype=_F32, device=x.device)
+    ws = torch.empty(_lib.get_lib().mf_proj_kde_ws_bytes(P, Bx * By) // 8, dtype=torch.int64, device=x.device)
+    wmax = weight_max(w)
+    call("mf_proj_whist2d_sums", ptr(x), ptr(w), ptr(wmax), x.shape[0], x.shape[1], ptr(V0), ptr(V1), P, ptr(ex), Bx,
+         ptr(ey), By, ptr(sums), ptr(ws), stream_ptr(x))
+    return sums
+
+
 KDE_PLAN_KERNELS = ("kde1d_fwd", "kde1d_bwd", "kde2d_fwd", "kde2d_bwd")
 KDE_PLAN_FIELDS = ("window", "block", "Pg", "groups", "per_wg", "split", "grid_x", "lds_bytes", "shift")   # MF_KDE_PLAN_*
 

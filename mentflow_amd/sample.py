@@ -544,6 +544,18 @@ class AnnealedImportanceSampler:
         self._gen = gen
         return self.last
 
+    @staticmethod
+    def _weights(res: dict) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(x, w = exp(logw - max logw) in fp32) of a run's dict: the largest weight is 1, a chain without weight has 0."""
+        logw = res["logw"]
+        return res["x"], torch.exp(logw - logw.max()).to(torch.float32)
+
+    def sample_weighted(self, prob_func: Callable, size: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Run the ladder and return the final states as they are, with their weights: (x [chains, ndim] fp32, w [chains]
+        fp32, w = exp(logw - max logw)) of ``run()``.  Nothing is resampled; `size` is ignored (there are `chains` rows).
+        The weighted histograms (``Histogram*.batched(..., weights=w)``, ``MENT.weighted``) consume the pair."""
+        return self._weights(self.run(_ment_of(prob_func, required_by=type(self).__name__)))
+
     def __call__(self, prob_func: Callable, size: int) -> torch.Tensor:
         owner = _ment_of(prob_func, required_by=type(self).__name__)
         res = self.run(owner)
@@ -683,6 +695,17 @@ class SequentialMonteCarloSampler(AnnealedImportanceSampler):
         if self.bridge_steps:
             self._at_target(args, base, x, logw, logp, accepted, self.bridge_steps)
         return self._finish(x, logw, logp, accepted, resampled, self.bridge_steps)
+
+    def sample_weighted(self, prob_func: Callable, size: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The population with its weights, (x [chains, ndim] fp32, w [chains] fp32, w = exp(logw - max logw)): walks the ladder
+        or bridges exactly as ``__call__`` decides, but neither forces the final resampling nor runs the collection rounds.
+        The population is kept with its unequalised log-weights, from which the next call bridges.  `size` is ignored."""
+        owner = _ment_of(prob_func, required_by=type(self).__name__)
+        if not self.persistent:
+            self.reset()
+        res = self.run(owner) if self.population is None else self._bridge(owner)
+        self.population = dict(x=res["x"], logw=res["logw"], logp=res["logp"])
+        return self._weights(res)
 
     def __call__(self, prob_func: Callable, size: int) -> torch.Tensor:
         owner = _ment_of(prob_func, required_by=type(self).__name__)

@@ -12,7 +12,7 @@ the same structure and values as the reference's either way; which path a measur
 from __future__ import annotations
 
 import logging
-from typing import Dict, List, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -112,21 +112,31 @@ def raw_sums(x: torch.Tensor, transforms: List[nn.Module], diagnostics: List[Lis
     return pieces, finish
 
 
-def forward(x: torch.Tensor, transforms: List[nn.Module], diagnostics: List[List[nn.Module]]) -> List[List[torch.Tensor]]:
-    """simulate.py:8-33: predictions[i][j] = diagnostics[i][j](transforms[i](x))."""
+def forward(x: torch.Tensor, transforms: List[nn.Module], diagnostics: List[List[nn.Module]],
+            weights: Optional[torch.Tensor] = None) -> List[List[torch.Tensor]]:
+    """simulate.py:8-33: predictions[i][j] = diagnostics[i][j](transforms[i](x)).  weights [n] (optional): one weight per
+    particle, handed to every fused group and every generic Histogram pair; any other generic diagnostic has no weighted
+    form and raises."""
     predictions: List[List[torch.Tensor]] = [[None] * len(diagnostics[i]) for i in range(len(transforms))]
     groups, generic = group_measurements(transforms, diagnostics)
     _log_plan(transforms, diagnostics, groups, generic)
+    if weights is not None:
+        for i, j in generic:
+            if not isinstance(diagnostics[i][j], Histogram):
+                raise NotImplementedError(
+                    f"weighted simulation: {type(diagnostics[i][j]).__name__} (measurement [{i}][{j}]) takes no particle "
+                    "weights; histogram diagnostics do (Histogram1D / Histogram2D)")
     for diagnostic, pre, slots, rows in groups.values():
         stacked = [torch.stack([r[k] for r in rows]) for k in range(len(rows[0]))]
-        hists = diagnostic.batched(apply_pre(x, pre), stacked)
+        hists = diagnostic.batched(apply_pre(x, pre), stacked, weights)
         for (i, j), h in zip(slots, hists.unbind(0)):
             predictions[i][j] = diagnostic._apply_noise(h)
     transported: Dict[int, torch.Tensor] = {}
     for i, j in generic:                                  # the reference's loop, one transform application per i
         if i not in transported:
             transported[i] = transforms[i](x.clone())     # simulate.py:32 (a user transform may work in place)
-        predictions[i][j] = diagnostics[i][j](transported[i])
+        predictions[i][j] = (diagnostics[i][j](transported[i]) if weights is None else
+                             diagnostics[i][j](transported[i], weights))
     return predictions
 
 
@@ -137,5 +147,5 @@ class Simulator:
         self.transforms = transforms
         self.diagnostics = diagnostics
 
-    def forward(self, x: torch.Tensor) -> List[List[torch.Tensor]]:
-        return forward(x, self.transforms, self.diagnostics)
+    def forward(self, x: torch.Tensor, weights: Optional[torch.Tensor] = None) -> List[List[torch.Tensor]]:
+        return forward(x, self.transforms, self.diagnostics, weights)
